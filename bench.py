@@ -26,11 +26,22 @@ timing (each env starts at a different `step_count`) and burns in one episode
 length; after that the same fraction of the batch is resetting in every call,
 as in any long-running job.  `--lockstep` keeps the synchronous episodes.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the headline line
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).
+With `--full` it also brackets kernels of the timed steps with HIP events and
+measures what the headline does not need; the JSON line then also carries
   roofline     achieved algorithmic GB/s of the raster kernel (HIP events around
-               every launch of the timed region) against the 8 TB/s HBM3E peak
+               every 8th launch of the timed region) against the 8 TB/s HBM3E peak
+  kernels_avg_us  the per-kernel averages of those events
+  value_sync_fault_check  the same steps with a host synchronisation + fault
+               check after every call (a window of its own, after the timed one)
   cpu_baseline the CPU oracle (a C port of the reference algorithm) timed on this
                box's host cores on a bounded sample of the same workload
+
+`--dump-outputs DIR` writes what the last timed step computed, as a caller of
+the timed path receives it, to DIR/<name>.npy (float32 / float64, at most
+64 MB; see dump_outputs).  The inputs (env seed, actions) are seeded: the same
+arguments give the same outputs on every run.
 """
 import argparse
 import json
@@ -45,6 +56,8 @@ sys.path.insert(0, os.path.join(REPO, 'moog.github.io_amd'))
 
 WORKLOAD = 'colliding_predators_32'
 ENVS_PER_GPU = 4096
+ACTION_SEED = 2024
+DUMP_BYTES = 60 * 1000 * 1000   # what --dump-outputs writes at most, all files together (< 64 MB)
 HBM_PEAK_GBPS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 
 
@@ -229,6 +242,95 @@ def launch_ranks(args):
     return subprocess.call(cmd, env=env)
 
 
+def kernel_figures(env, args, n, every):
+    """(--full) The per-kernel HIP-event averages of the timed steps and the roofline of the kernel that dominates."""
+    from moog import _abi
+    P = env.compiled.program
+    k_ms = {'raster': env.kernel_time(_abi.MOOG_K_RASTER), 'step': env.kernel_time(_abi.MOOG_K_STEP),
+            'reset': env.kernel_time(_abi.MOOG_K_RESET)}
+    frames = args.phase in ('full', 'render')
+    if frames:
+        rb = raster_bytes_per_env(env)
+        r_ms, r_n = k_ms['raster']
+        roof_kernel = raster_kernel_name(env)
+        tr = raster_traffic(args.workload, n)
+    else:
+        # No frames in this phase: the launch that dominates is the step kernel.  Its algorithmic bytes (SURVEY 8d B_phys: the
+        # mutable sprite state read and written once, the per-sprite parameters read, the action; sub-steps stay on chip):
+        # S x (6 x 8 + 6 x 8 + 1) + S x 56 + 16 bytes per env-step.  It is a latency-bound O(S^2) geometry kernel: the HBM
+        # fraction is reported because the contract asks for one, not because HBM bounds it.
+        rb = float(P.n_slots * 153 + 16)
+        r_ms, r_n = k_ms['step']
+        roof_kernel = 'moog_step_kernel (csrc/moog_kernels.h; not HBM-bound: one wavefront per env, dependent fp64 chain)'
+        tr = None
+    r_avg_s = (r_ms / max(r_n, 1)) * 1e-3
+    achieved = (n * rb / r_avg_s) / 1e9 if r_avg_s > 0 else 0.0
+    return {
+        'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
+                     'frac': achieved / HBM_PEAK_GBPS,
+                     'traffic': tr['traffic_bytes'] if tr else None,
+                     'traffic_source': (tr.get('source', 'profiles/raster_traffic.json') + ' (offline rocprofv3 PMC passes, '
+                                        'not this run)') if tr else None,
+                     'algorithmic_bytes_per_launch': n * rb,
+                     'kernel': roof_kernel, 'avg_kernel_us': r_avg_s * 1e6, 'kernel_samples': int(r_n),
+                     'algorithmic_bytes_per_env': rb},
+        'kernels_avg_us': {k: (v[0] / max(v[1], 1)) * 1e3 for k, v in k_ms.items() if v[1] > 0},
+        'kernels_avg_us_note': 'HIP-event brackets around every %dth launch inside the timed region' % every,
+    }
+
+
+def dump_outputs(directory, env, phase):
+    """Writes what the last timed step handed its caller to directory/<name>.npy (float64; frames float32).  The
+    TimeStep a step returns views the env's buffers (step_type, reward, discount; its frame observations are env.image):
+    full / step: step_type, reward, discount (every env) and, with frames, image; render: the frames; physics (the call
+    returns nothing): the state records it advanced.  Where every env's frames / state records would not fit in
+    DUMP_BYTES beside the rest, those of a fixed sample of envs are written (seeded, sorted): sample_env_index.npy
+    lists them.  Only this process's envs (rank 0's shard when N > 1).
+
+    Every value written is finite.  The engine encodes dm_env's None as NaN (include/moog_engine.h): reward and
+    discount are None in the envs that began an episode in this call, and are written as 0 there (step_type.npy,
+    0 = FIRST, says which envs those are); in the state records NaN also stands for fields a config left unset, so
+    state_f64 is written with 0 in place of its non-finite entries and state_f64_nonfinite.npy says where they were
+    (1 NaN, 2 +inf, 3 -inf).  Any other non-finite output is an error."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    n = env.num_envs
+    out = {}
+    if phase in ('full', 'step'):
+        out['step_type'] = env.step_type.to(torch.float64)
+        first = env.step_type == 0   # dm_env.StepType.FIRST
+        for key in ('reward', 'discount'):
+            t = getattr(env, key).to(torch.float64)
+            out[key] = torch.where(first, torch.zeros_like(t), t)
+    if phase == 'physics':
+        per_env = [('state_f64', env.state_f64, torch.float64), ('state_i32', env.state_i32, torch.float64)]
+    elif phase in ('full', 'render'):
+        per_env = [('image', env.image, torch.float32)]
+    else:
+        per_env = []
+    if per_env:
+        row = sum(t[0].numel() * (8 if dt == torch.float64 else 4) for _, t, dt in per_env) + 8   # (+ its sample_env_index entry)
+        if phase == 'physics':
+            row += env.state_f64[0].numel() * 8   # (state_f64_nonfinite)
+        k = max(1, min(n, (DUMP_BYTES - 8 * n * len(out)) // row))
+        idx = np.arange(n) if k == n else np.sort(np.random.RandomState(0).choice(n, k, replace=False))
+        sel = torch.as_tensor(idx, device=env.device)
+        for key, t, dt in per_env:
+            out[key] = t.index_select(0, sel).to(dt)
+        out['sample_env_index'] = torch.as_tensor(idx, dtype=torch.float64)
+    if 'state_f64' in out:
+        x = out['state_f64']
+        out['state_f64_nonfinite'] = (torch.isnan(x) * 1.0 + (x == float('inf')) * 2.0 + (x == float('-inf')) * 3.0).to(torch.float64)
+        out['state_f64'] = torch.where(torch.isfinite(x), x, torch.zeros_like(x))
+    bad = sorted(key for key, t in out.items() if not bool(torch.isfinite(t).all()))
+    if bad:
+        raise RuntimeError('non-finite outputs of the last timed step: %s' % ', '.join(bad))
+    for key, t in out.items():
+        np.save(os.path.join(directory, key + '.npy'), t.cpu().numpy())
+    return sorted(out)
+
+
 def stagger_episodes(env, timeout, index0):
     """De-synchronises the episodes: env i starts its first episode at step_count
     (i * 7919) mod timeout (7919 is prime: a contiguous shard of the env axis covers all
@@ -256,11 +358,16 @@ def main():
                          '"physics-only (no observer)", is --workload chase_avoid_torus --phase step); physics = '
                          'env.physics.step alone (:101-107, moog_engine_physics_only); render = env.observation() alone (:113-130, '
                          'moog_engine_render)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: per-kernel HIP-event times and the roofline of the '
+                         'timed steps, the strict-fault-check window, the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip the CPU baseline')
     ap.add_argument('--no-schedule', action='store_true', help='disable cost-ordered launch')
     ap.add_argument('--no-fused', action='store_true', help='(accepted and ignored: the launch structure it switched off was retired with ABI 30)')
     ap.add_argument('--lockstep', action='store_true', help='keep the episodes of the batch synchronous')
-    ap.add_argument('--no-extras', action='store_true', help='skip the strict-fault-check comparison window')
+    ap.add_argument('--no-extras', action='store_true', help='(--full) skip the strict-fault-check comparison window')
     ap.add_argument('--no-spec', action='store_true',
                     help='step with the generic kernels even if one specialised for the program exists (moog/_spec.py)')
     ap.add_argument('--sub-batches', type=int, default=1,
@@ -268,6 +375,8 @@ def main():
                          '(moog.environment.SubBatchedEnvironment): an ADDITIONAL line, the synchronous whole-batch '
                          'step is the headline')
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_extras = True
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args))
@@ -354,12 +463,15 @@ def main():
     staggered = (not args.lockstep) and timeout == timeout and 1 < timeout < 1e6
 
     # Synthetic input: random actions drawn on the device BEFORE the timed region (the inputs are resident in HBM
-    # when it starts): a ring of action batches, one per step of the window (at most 1024, then it wraps).
+    # when it starts): a ring of action batches, one per step of the window (at most 1024, then it wraps).  Drawn from a
+    # generator of their own with a fixed seed: the same arguments give the same actions on every run.
     ring = max(1, min(1024, args.steps))
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(ACTION_SEED + rank)
     if is_grid:
-        acts = torch.randint(0, 5, (ring, n), dtype=torch.int32, device=dev)
+        acts = torch.randint(0, 5, (ring, n), dtype=torch.int32, device=dev, generator=gen)
     else:
-        acts = torch.empty((ring, n, 2), dtype=torch.float64, device=dev).uniform_(-1.0, 1.0)
+        acts = torch.empty((ring, n, 2), dtype=torch.float64, device=dev).uniform_(-1.0, 1.0, generator=gen)
     step_no = [0]
 
     m = n // G
@@ -406,17 +518,22 @@ def main():
     # averages (and the roofline figure of the raster kernel) are measurements of the timed steps
     # themselves.  Every 8th launch of each kernel is bracketed (25 samples per kernel in the default window,
     # never fewer than 10): bracketing every launch costs the timed region 20 us per step (2 %), measured.
+    # (--full only: the headline needs none of it)
     every = max(1, min(8, args.steps // 10))
-    env.set_timing(True, every=every)
-    for k in range(_abi.MOOG_K_COUNT):
-        env.kernel_time(k)   # clear
+    if args.full:
+        env.set_timing(True, every=every)
+        for k in range(_abi.MOOG_K_COUNT):
+            env.kernel_time(k)   # clear
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         one_step()
     barrier()
     dt = time.perf_counter() - t0
-    env.set_timing(False)
+    if args.full:
+        env.set_timing(False)
+    if args.dump_outputs and rank == 0:   # (before anything else steps the batch)
+        dump_outputs(args.dump_outputs, env, args.phase)
     # MAX over ranks, off the timed path (RCCL needs the tensor on the GPU, gloo on the host)
     rdev = dev if backend == 'nccl' else None
     dt_max = sharding.max_over_ranks(dt, device=rdev)
@@ -426,8 +543,6 @@ def main():
     rate_max = sharding.reduce_over_ranks([n * args.steps / dt], 'max', device=rdev)[0]
     env.raise_faults()   # faults of the timed steps (deferred surfacing: none were skipped silently)
 
-    k_ms = {'raster': env.kernel_time(_abi.MOOG_K_RASTER), 'step': env.kernel_time(_abi.MOOG_K_STEP),
-            'reset': env.kernel_time(_abi.MOOG_K_RESET)}
     extras = {}
     if rank == 0 and world == 1 and not args.no_extras:
         # the same steps with a host synchronisation + fault check after every call
@@ -444,23 +559,6 @@ def main():
     faults = int((env.state_i32[:, env.layout.o_fault] != 0).sum().item())
     if rank == 0:
         total_steps = int(envs_seen) * args.steps
-        frames = args.phase in ('full', 'render')
-        if frames:
-            rb = raster_bytes_per_env(env)
-            r_ms, r_n = k_ms['raster']
-            roof_kernel = raster_kernel_name(env)
-            tr = raster_traffic(args.workload, n)
-        else:
-            # No frames in this phase: the launch that dominates is the step kernel.  Its algorithmic bytes (SURVEY 8d B_phys: the
-            # mutable sprite state read and written once, the per-sprite parameters read, the action; sub-steps stay on chip):
-            # S x (6 x 8 + 6 x 8 + 1) + S x 56 + 16 bytes per env-step.  It is a latency-bound O(S^2) geometry kernel: the HBM
-            # fraction is reported because the contract asks for one, not because HBM bounds it.
-            rb = float(P.n_slots * 153 + 16)
-            r_ms, r_n = k_ms['step']
-            roof_kernel = 'moog_step_kernel (csrc/moog_kernels.h; not HBM-bound: one wavefront per env, dependent fp64 chain)'
-            tr = None
-        r_avg_s = (r_ms / max(r_n, 1)) * 1e-3
-        achieved = (n * rb / r_avg_s) / 1e9 if r_avg_s > 0 else 0.0
         line = {
             'metric': 'env steps/sec (whole node), %d envs x %d sprites, %dx%d obs' % (
                 n, P.n_slots, P.render.height, P.render.width) + ('' if args.phase == 'full' else ' [phase: %s]' % args.phase),
@@ -497,22 +595,14 @@ def main():
                                        else 'generic (moog_step_kernel reading the program at run time)'),
                        'episodes': ('staggered (step_count offsets + %d burn-in steps before the warm-up)' % burn_in)
                                    if staggered else 'lockstep'},
-            'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
-                         'frac': achieved / HBM_PEAK_GBPS,
-                         'traffic': tr['traffic_bytes'] if tr else None,
-                         'traffic_source': (tr.get('source', 'profiles/raster_traffic.json') + ' (offline rocprofv3 PMC passes, '
-                                            'not this run)') if tr else None,
-                         'algorithmic_bytes_per_launch': n * rb,
-                         'kernel': roof_kernel, 'avg_kernel_us': r_avg_s * 1e6, 'kernel_samples': int(r_n),
-                         'algorithmic_bytes_per_env': rb},
-            'kernels_avg_us': {k: (v[0] / max(v[1], 1)) * 1e3 for k, v in k_ms.items() if v[1] > 0},
-            'kernels_avg_us_note': 'HIP-event brackets around every %dth launch inside the timed region' % every,
             'faulted_envs': faults,
         }
+        if args.full:
+            line.update(kernel_figures(env, args, n, every))
         line.update(extras)
         if world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(args.workload, phase=args.phase)
-        elif world > 1:
+        elif world > 1 and args.full:
             line['cpu_baseline'] = None
             line['cpu_baseline_note'] = 'timed by the --gpus 1 run only (rank 0, N = 1)'
         print(json.dumps(line))

@@ -1,6 +1,5 @@
 """CPU-only checks of the host side: config lowering, ABI symbols, layout."""
 import ctypes
-import importlib.util
 import os
 
 import numpy as np
@@ -10,7 +9,6 @@ import helpers
 from moog import _abi, _compiler, _engine
 from moog_demos import example_configs
 
-REF = '/root/reference/moog_demos/example_configs'
 PKG = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'moog.github.io_amd')
 
 
@@ -128,7 +126,6 @@ def test_missing_library_fails_loudly(tmp_path):
         _engine.load_library(str(tmp_path / 'nope.so'))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference checkout not present')
 @pytest.mark.parametrize('name,level', [('pong', 0), ('chase_avoid_torus', 0), ('colliding_predators', 0),
                                         ('functional_maze', 0), ('falling_balls', 0),
                                         ('first_person_predators_prey', 0), ('cleanup', 0), ('pacman', 0),
@@ -140,13 +137,12 @@ def test_missing_library_fails_loudly(tmp_path):
                                         ('red_green', 0), ('red_green', 1), ('red_green', 2), ('red_green', 3)])
 def test_reference_configs_load_unchanged(name, level):
     """The reference's own config files import this repo's `moog` and lower to the
-    same program as the re-stated recipes."""
-    spec = importlib.util.spec_from_file_location('ref_' + name, os.path.join(REF, name + '.py'))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    ref = _compiler.compile_config(layer_capacity=example_configs.capacity(name), **m.get_config(level))
+    same program as the re-stated recipes.  The programs they lower to are stored in
+    tests/golden/reference_programs.npz (tests/golden/make_reference_programs.py)."""
+    with np.load(os.path.join(helpers.GOLDEN, 'reference_programs.npz')) as g:
+        ref = g['%s_l%d' % (name, level)].tobytes()
     mine = helpers.compiled(name if level == 0 else '%s_l%d' % (name, level))
-    assert bytes(ref.program) == bytes(mine.program)
+    assert ref == bytes(mine.program)
 
 
 def test_program_contents():

@@ -6,14 +6,14 @@
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04; rm -rf $O; mkdir -p $O
 W=$GRAFT_REPO_ROOT/tools/ubench/build
-echo "== default bench (python bench.py)" > $O/bench.txt
-python bench.py 2>/dev/null | tail -1 >> $O/bench.txt
-echo "== python bench.py --no-fused --no-cpu-baseline" >> $O/bench.txt
-python bench.py --no-fused --no-cpu-baseline 2>/dev/null | tail -1 >> $O/bench.txt
-echo "== GPU_MAX_HW_QUEUES=8 python bench.py --sub-batches 2 --no-cpu-baseline" >> $O/bench.txt
-GPU_MAX_HW_QUEUES=8 python bench.py --sub-batches 2 --no-cpu-baseline 2>/dev/null | tail -1 >> $O/bench.txt
-echo "== python bench.py --workload falling_balls_64 --envs-per-gpu 8192 --no-cpu-baseline" >> $O/bench.txt
-python bench.py --workload falling_balls_64 --envs-per-gpu 8192 --no-cpu-baseline 2>/dev/null | tail -1 >> $O/bench.txt
+echo "== default bench (python bench.py --full)" > $O/bench.txt
+python bench.py --full 2>/dev/null | tail -1 >> $O/bench.txt
+echo "== python bench.py --full --no-fused --no-cpu-baseline" >> $O/bench.txt
+python bench.py --full --no-fused --no-cpu-baseline 2>/dev/null | tail -1 >> $O/bench.txt
+echo "== GPU_MAX_HW_QUEUES=8 python bench.py --full --sub-batches 2 --no-cpu-baseline" >> $O/bench.txt
+GPU_MAX_HW_QUEUES=8 python bench.py --full --sub-batches 2 --no-cpu-baseline 2>/dev/null | tail -1 >> $O/bench.txt
+echo "== python bench.py --full --workload falling_balls_64 --envs-per-gpu 8192 --no-cpu-baseline" >> $O/bench.txt
+python bench.py --full --workload falling_balls_64 --envs-per-gpu 8192 --no-cpu-baseline 2>/dev/null | tail -1 >> $O/bench.txt
 python tools/r04_exp.py --args "--no-fused --no-cpu-baseline --no-extras --steps 100 --warmup 10" \
   'n1024=@--envs-per-gpu 1024' 'n2048=@--envs-per-gpu 2048' 'n4096=' 'n8192=@--envs-per-gpu 8192' 'n16384=@--envs-per-gpu 16384' \
   'sub2=GPU_MAX_HW_QUEUES=8;@--sub-batches 2' 'sub4=GPU_MAX_HW_QUEUES=16;@--sub-batches 4' 'sub8=GPU_MAX_HW_QUEUES=16;@--sub-batches 8' \

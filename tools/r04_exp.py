@@ -31,7 +31,7 @@ def main():
             else:
                 k, _, v = kv.partition('=')
                 env[k] = v
-        cmd = [sys.executable, os.path.join(REPO, 'bench.py')] + base + extra
+        cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--full'] + base + extra
         p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         line = None
         for ln in p.stdout.splitlines():

@@ -6,16 +6,16 @@ O=gpurun_out/r05; rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp
 line() { echo "== $*" >> $O/bench.txt; "$@" 2>/dev/null | tail -1 >> $O/bench.txt; }
 echo -n > $O/bench.txt
-line python bench.py
-line python bench.py --no-cpu-baseline
-line python bench.py --no-cpu-baseline --no-spec
-line python bench.py --no-cpu-baseline --no-schedule
-line env GPU_MAX_HW_QUEUES=8 python bench.py --sub-batches 2 --no-cpu-baseline
-line python bench.py --envs-per-gpu 8192 --no-cpu-baseline
-line python bench.py --envs-per-gpu 16384 --no-cpu-baseline
-line python bench.py --workload falling_balls_64 --envs-per-gpu 8192 --no-cpu-baseline
-line python bench.py --workload falling_balls_64 --envs-per-gpu 8192 --no-cpu-baseline --no-spec
-line python bench.py --workload chase_avoid_torus --no-cpu-baseline
+line python bench.py --full
+line python bench.py --full --no-cpu-baseline
+line python bench.py --full --no-cpu-baseline --no-spec
+line python bench.py --full --no-cpu-baseline --no-schedule
+line env GPU_MAX_HW_QUEUES=8 python bench.py --full --sub-batches 2 --no-cpu-baseline
+line python bench.py --full --envs-per-gpu 8192 --no-cpu-baseline
+line python bench.py --full --envs-per-gpu 16384 --no-cpu-baseline
+line python bench.py --full --workload falling_balls_64 --envs-per-gpu 8192 --no-cpu-baseline
+line python bench.py --full --workload falling_balls_64 --envs-per-gpu 8192 --no-cpu-baseline --no-spec
+line python bench.py --full --workload chase_avoid_torus --no-cpu-baseline
 python tools/bench_configs.py > $O/bench_configs.txt 2>&1
 MOOG_STEP_SPEC=0 python tools/bench_configs.py > $O/bench_configs_generic.txt 2>&1
 bash tools/bench_ranks.sh > $O/bench_ranks.txt 2>&1

@@ -8,11 +8,11 @@ key = None
 for l in lines:
     if l.startswith('=='): key = l[3:].strip()
     elif l.startswith('{'): bench[key] = json.loads(l)
-h = bench['python bench.py']
-sub = bench['env GPU_MAX_HW_QUEUES=8 python bench.py --sub-batches 2 --no-cpu-baseline']
-e8, e16 = bench['python bench.py --envs-per-gpu 8192 --no-cpu-baseline'], bench['python bench.py --envs-per-gpu 16384 --no-cpu-baseline']
-c5 = bench['python bench.py --workload falling_balls_64 --envs-per-gpu 8192 --no-cpu-baseline']
-c2 = bench['python bench.py --workload chase_avoid_torus --no-cpu-baseline']
+h = bench['python bench.py --full']
+sub = bench['env GPU_MAX_HW_QUEUES=8 python bench.py --full --sub-batches 2 --no-cpu-baseline']
+e8, e16 = bench['python bench.py --full --envs-per-gpu 8192 --no-cpu-baseline'], bench['python bench.py --full --envs-per-gpu 16384 --no-cpu-baseline']
+c5 = bench['python bench.py --full --workload falling_balls_64 --envs-per-gpu 8192 --no-cpu-baseline']
+c2 = bench['python bench.py --full --workload chase_avoid_torus --no-cpu-baseline']
 M = lambda j: '%.2f M' % (j['value'] / 1e6)
 cfg = {}
 for l in open(os.path.join(O, 'bench_configs.txt')):

@@ -16,7 +16,7 @@ PY
 for rep in 1 2; do
 for v in base maxilp maxmem ifcvt iterilp trackers; do
   d=""; [ $v != base ] && d=$PWD/gpurun_in/spec_$v
-  env ${d:+MOOG_SPEC_DIR=$d} ${d:+MOOG_SPEC_PREBUILT=1} python bench.py --no-extras --no-cpu-baseline > $out/${v}_$rep.log 2>&1; show $out/${v}_$rep.log $v
-  [ $rep = 1 ] && { env ${d:+MOOG_SPEC_DIR=$d} ${d:+MOOG_SPEC_PREBUILT=1} python bench.py --no-extras --no-cpu-baseline --workload falling_balls_64 --envs-per-gpu 8192 --steps 30 --warmup 5 > $out/${v}_c5.log 2>&1; show $out/${v}_c5.log ${v}_c5; }
+  env ${d:+MOOG_SPEC_DIR=$d} ${d:+MOOG_SPEC_PREBUILT=1} python bench.py --full --no-extras --no-cpu-baseline > $out/${v}_$rep.log 2>&1; show $out/${v}_$rep.log $v
+  [ $rep = 1 ] && { env ${d:+MOOG_SPEC_DIR=$d} ${d:+MOOG_SPEC_PREBUILT=1} python bench.py --full --no-extras --no-cpu-baseline --workload falling_balls_64 --envs-per-gpu 8192 --steps 30 --warmup 5 > $out/${v}_c5.log 2>&1; show $out/${v}_c5.log ${v}_c5; }
 done
 done

@@ -16,8 +16,8 @@ PY
 for rep in 1 2; do
 for v in wide nowide; do
   d=""; [ $v != wide ] && d=$PWD/gpurun_in/spec_$v
-  env ${d:+MOOG_SPEC_DIR=$d} ${d:+MOOG_SPEC_PREBUILT=1} python bench.py --no-extras --no-cpu-baseline > $out/${v}_$rep.log 2>&1; show $out/${v}_$rep.log $v
-  env ${d:+MOOG_SPEC_DIR=$d} ${d:+MOOG_SPEC_PREBUILT=1} python bench.py --no-extras --no-cpu-baseline --workload falling_balls_64 --envs-per-gpu 8192 --steps 30 --warmup 5 > $out/${v}_c5_$rep.log 2>&1; show $out/${v}_c5_$rep.log ${v}_c5
+  env ${d:+MOOG_SPEC_DIR=$d} ${d:+MOOG_SPEC_PREBUILT=1} python bench.py --full --no-extras --no-cpu-baseline > $out/${v}_$rep.log 2>&1; show $out/${v}_$rep.log $v
+  env ${d:+MOOG_SPEC_DIR=$d} ${d:+MOOG_SPEC_PREBUILT=1} python bench.py --full --no-extras --no-cpu-baseline --workload falling_balls_64 --envs-per-gpu 8192 --steps 30 --warmup 5 > $out/${v}_c5_$rep.log 2>&1; show $out/${v}_c5_$rep.log ${v}_c5
 done
 done
 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -n 3 -k "teacher_forced or free_running or full_size or pile or specialised or own_rng" > $out/pytest.log 2>&1

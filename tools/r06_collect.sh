@@ -6,22 +6,22 @@ O=gpurun_out/r06; rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp
 line() { echo "== $*" >> $O/bench.txt; "$@" 2>/dev/null | tail -1 >> $O/bench.txt; }
 echo -n > $O/bench.txt
-line python bench.py
-line python bench.py --no-cpu-baseline
-line env MOOG_DRAW_IN_STEP=0 python bench.py --no-cpu-baseline
-line python bench.py --no-cpu-baseline --no-spec
-line python bench.py --no-cpu-baseline --no-schedule
-line env GPU_MAX_HW_QUEUES=8 python bench.py --sub-batches 2 --no-cpu-baseline
-line python bench.py --envs-per-gpu 8192 --no-cpu-baseline
-line python bench.py --envs-per-gpu 16384 --no-cpu-baseline
-line python bench.py --no-cpu-baseline --phase step
-line python bench.py --no-cpu-baseline --phase physics
-line python bench.py --no-cpu-baseline --phase render
-line python bench.py --workload chase_avoid_torus --phase step
-line python bench.py --workload chase_avoid_torus --no-cpu-baseline
-line python bench.py --workload functional_maze@128 --envs-per-gpu 8192
-line python bench.py --workload falling_balls_64 --envs-per-gpu 8192
-line env MOOG_RASTER_COMPACT=0 python bench.py --workload falling_balls_64 --envs-per-gpu 8192 --no-cpu-baseline
+line python bench.py --full
+line python bench.py --full --no-cpu-baseline
+line env MOOG_DRAW_IN_STEP=0 python bench.py --full --no-cpu-baseline
+line python bench.py --full --no-cpu-baseline --no-spec
+line python bench.py --full --no-cpu-baseline --no-schedule
+line env GPU_MAX_HW_QUEUES=8 python bench.py --full --sub-batches 2 --no-cpu-baseline
+line python bench.py --full --envs-per-gpu 8192 --no-cpu-baseline
+line python bench.py --full --envs-per-gpu 16384 --no-cpu-baseline
+line python bench.py --full --no-cpu-baseline --phase step
+line python bench.py --full --no-cpu-baseline --phase physics
+line python bench.py --full --no-cpu-baseline --phase render
+line python bench.py --full --workload chase_avoid_torus --phase step
+line python bench.py --full --workload chase_avoid_torus --no-cpu-baseline
+line python bench.py --full --workload functional_maze@128 --envs-per-gpu 8192
+line python bench.py --full --workload falling_balls_64 --envs-per-gpu 8192
+line env MOOG_RASTER_COMPACT=0 python bench.py --full --workload falling_balls_64 --envs-per-gpu 8192 --no-cpu-baseline
 python tools/bench_configs.py > $O/bench_configs.txt 2>&1
 bash tools/bench_ranks.sh > $O/bench_ranks.txt 2>&1
 python tools/step_tail.py colliding_predators_32 4096 60 2>&1 | grep -v amdgpu > $O/step_tail.txt
