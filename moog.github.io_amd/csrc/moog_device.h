@@ -655,9 +655,9 @@ __device__ __forceinline__ int nth_set_bit32(unsigned m, int k) {
 }
 
 #define CAND_SKIP 0xFFFF   // a candidate entry struck from the list (collision_same_layer): counts as rejected
-// G lanes per candidate: 16 (four candidates a batch), or -- with -DMOOG_WIDE_BATCH -- 32 (two) for polygons of 17 - 32
-// vertices: falling_balls_64's 30-gons never fit sixteen lanes and each of its candidates takes the whole wave's path test.
-// Exact either way (the parity suite passes with it); not faster, see narrow_reject_prefix below.
+// G lanes per candidate: 16 (four candidates a batch).  G = 32 (two) for polygons of 17 - 32 vertices -- falling_balls_64's
+// 30-gons never fit sixteen lanes and each of its candidates takes the whole wave's path test -- is exact too, and was not
+// faster (profiles/r05_step_experiments.txt: falling_balls_64 +0.7 %, colliding_predators_32 -2 %).
 template <int G>
 __device__ inline int narrow_reject_prefix_g(const Env& e, int c, int n) {
   constexpr int SH = G == 16 ? 4 : 5;
@@ -736,9 +736,6 @@ __device__ inline int narrow_reject_prefix_g(const Env& e, int c, int n) {
 
 __device__ inline int narrow_reject_prefix(const Env& e, int c, int n) {
   const int r = narrow_reject_prefix_g<16>(e, c, n);
-#ifdef MOOG_WIDE_BATCH   // measured (profiles/r05_step_experiments.txt): falling_balls_64 +0.7 %, colliding_predators_32 -2 %: off
-  if (r < 0) return narrow_reject_prefix_g<32>(e, c, n < 2 ? n : 2);
-#endif
   return r < 0 ? 0 : r;
 }
 
@@ -1669,9 +1666,7 @@ __device__ inline void force_pair_newton(Env& e, PForce F, int s0, int s1, int K
     } else if (F->kind == MOOG_FORCE_DISTANCE_SPRING) {
       mag = -1. * F->p0 * (dist - F->p1);
     } else if (F->kind == MOOG_FORCE_DISTANCE_EXPR) {   // any force_fn(distance), traced (the kernels with the expression VM)
-#ifndef MOOG_NO_DISTANCE_EXPR   // (A/B builds)
       if constexpr (DYN) { e.xarg = dist; mag = eval_expr(e, F->i0, s0, s1, nullptr, nullptr); }
-#endif
     }
     f1x = mag * ux; f1y = mag * uy;
     if (F->symmetric) { f0x = -1 * f1x; f0y = -1 * f1y; }

@@ -57,7 +57,6 @@ struct moog_engine {
   int step_wps = 4;   // register-allocation variant of the step kernel (waves per SIMD)
   void* spec_handle = nullptr;   // a step kernel compiled for this very program (load_spec_kernel), or null
   void (*spec_launch)(int, size_t, hipStream_t, const KArgs*) = nullptr;
-  int prio_pm[3] = {0, 0, 0};   // wave priorities by launch rank, per mille of the batch (KArgs::prio_t)
   int32_t xstack_off = 0;
   FOp* d_fops = nullptr;        // flattened force list (moog_flatten_forces)
   int32_t n_fops = 0;
@@ -72,9 +71,6 @@ struct moog_engine {
   RmSetup mask_setup{};   // the mask rasteriser (moog_raster_mask_core.h): ok = this program's ordinary frames are drawn by it
   uint8_t* draw = nullptr;        // its input: a draw record per env (moog_draw_record.h), written by the step kernel or derived before the launch
   RmDrawLayout draw_lay{};
-  int raster_persist = 0;         // MOOG_RASTER_PERSIST=k: frames per CU the mask rasteriser's launch keeps resident (one round of workgroups that draw several frames each); 0: a workgroup per frame
-  int n_cus = 256;
-  bool draw_in_step = true;       // MOOG_DRAW_IN_STEP=0: never by the step kernel (A/B runs, tests: the derive kernel for every launch)
   int raster_tile_w = 0, raster_band_h = 0, raster_tiles_x = 1, raster_bands = 1;   // one workgroup per tile of the canvas
   // anti_aliasing > 1: frames are drawn on a canvas aa x the observation (a chunk of envs at a time) and down-sampled
   int aa = 1, canvas_w = 0, canvas_h = 0, aa_chunk = 0;
@@ -96,7 +92,7 @@ struct moog_engine {
   static constexpr int POOL_STREAMS = 8;
   int pool_streams = 2;   // the ones in use: hardware queues the runtime has (GPU_MAX_HW_QUEUES, default 4) minus the caller's and the sort's
   bool pool_on = false, pool_ready = false;
-  int pool_depth = 2;              // records per env: the next episode and the one after (an episode shorter than a fill does not stall its call)
+  static constexpr int pool_depth = 2;   // records per env: the next episode and the one after (an episode shorter than a fill does not stall its call)
   int32_t* pool_state = nullptr;   // [pool_depth][n_envs] 0 empty / 3 claimed / 1 being filled / 2 ready
   int32_t* pool_tag = nullptr;     // [pool_depth][n_envs] episode of the pool record
   int32_t* pool_lock = nullptr;    // [n_envs] 4 while the step kernel opens an episode of the env
@@ -234,7 +230,6 @@ static StepVariant step_variant_of(const moog_program_t* prog) {
     v.xstack_off = (int32_t)v.step_lds;
     v.step_lds += (size_t)prog->xstack_depth * 64 * 8;
   }
-  { const char* pad = getenv("MOOG_LDS_PAD"); if (pad) v.step_lds += (size_t)atoi(pad); }  // occupancy experiments
   for (int r = 0; r < prog->n_rules; ++r) {
     int k = prog->rules[r].kind;
     if (k == MOOG_RULE_VANISH_BY_FILTER || k == MOOG_RULE_CHANGE_LAYER || k == MOOG_RULE_CREATE_SPRITES ||
@@ -298,16 +293,9 @@ static StepVariant step_variant_of(const moog_program_t* prog) {
     v.late_reset = !stepping && !(off && atoi(off));
     if (v.late_reset) v.dynamic_rules = true;   // (the variant with the expression evaluator)
   }
-  {   // MOOG_STEP_VARIANT=t|m (experiments): run a program on a kernel variant that carries more than it needs (what the variant
-      // itself costs: profiles/r04_variant_tax.txt)
-    const char* sv = getenv("MOOG_STEP_VARIANT");
-    if (sv && (sv[0] == 't' || sv[0] == 'm')) v.dynamic_rules = true;
-    if (sv && sv[0] == 'm') { v.maze_kernel = true; v.late_reset = false; }
-  }
   // register allocation: three waves per SIMD (168 VGPRs) when the LDS of an env allows no more than 14 envs per CU anyway
   v.wps = (160 * 1024 / (v.step_lds ? v.step_lds : 1)) <= 14 ? 3 : 4;
-  { const char* w = getenv("MOOG_STEP_WPS"); if (w && (atoi(w) == 3 || atoi(w) == 4)) v.wps = atoi(w); }   // experiments
-  { const char* w = getenv("MOOG_STEP_WPS"); if (w && atoi(w) == 2 && !v.dynamic_rules && !(v.maze_kernel && !v.late_reset)) v.wps = 2; }   // (plain programs only)
+  { const char* w = getenv("MOOG_STEP_WPS"); if (w && (atoi(w) == 3 || atoi(w) == 4)) v.wps = atoi(w); }   // experiments, tests
   return v;
 }
 
@@ -495,7 +483,6 @@ static void mask_plan_rows(moog_engine* e, int cap) {
   }
   ms.cap_rows = cap;
   ms.lds = ms.plan.total;
-  { const char* pad = getenv("MOOG_RASTER_LDS_PAD"); if (pad && ms.lds + (uint32_t)atoi(pad) <= 64u * 1024u) ms.lds += (uint32_t)atoi(pad); }  // occupancy experiments
   if (ms.plan.total > 64u * 1024u) ms.ok = 0;
 }
 
@@ -642,7 +629,6 @@ int moog_engine_create(const moog_program_t* prog, int32_t n_envs, int32_t devic
       if (e->canvas_h > 128 && e->canvas_h <= 256 && e->aa <= 1 && !(sw && atoi(sw) == 0) && env_prefix_slots(prog, &nsv_) >= 32)
         e->raster_band_h = e->canvas_h;
     }
-    { const char* bh = getenv("MOOG_RASTER_BAND_H"); if (bh && atoi(bh) >= 16 && atoi(bh) <= e->canvas_h) e->raster_band_h = atoi(bh); }   // experiments
     e->raster_bands = (e->canvas_h + e->raster_band_h - 1) / e->raster_band_h;
     int W = e->raster_tile_w, H = e->raster_band_h;   // (the LDS plan is per tile)
     int ncopy = prog->render.polymod == MOOG_POLYMOD_TORUS ? 9 : 1;
@@ -684,7 +670,6 @@ int moog_engine_create(const moog_program_t* prog, int32_t n_envs, int32_t devic
     e->raster_chunk = cap;
     e->raster_plan_ = pl;
     e->raster_lds = pl.total;
-    { const char* pad = getenv("MOOG_RASTER_LDS_PAD"); if (pad) e->raster_lds += (size_t)atoi(pad); }  // occupancy experiments
   }
   {   // mask rasteriser (moog_raster_mask_core.h): one-tile frames, polygons of <= 128 vertices, at most 256 polygons (a torus has nine per sprite)
     RmSetup& ms = e->mask_setup;
@@ -727,10 +712,6 @@ int moog_engine_create(const moog_program_t* prog, int32_t n_envs, int32_t devic
           free_engine(e);
           return fail(MOOG_E_NOMEM, "out of device memory (draw records)");
         }
-        const char* ds = getenv("MOOG_DRAW_IN_STEP");
-        e->draw_in_step = !(ds && atoi(ds) == 0);
-        { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) == hipSuccess && cus > 0) e->n_cus = cus; }
-        { const char* ps = getenv("MOOG_RASTER_PERSIST"); if (ps) e->raster_persist = atoi(ps); }
       }
     }
   }
@@ -738,16 +719,6 @@ int moog_engine_create(const moog_program_t* prog, int32_t n_envs, int32_t devic
     int (*const configure[6])(size_t) = {moog_configure_step_f3, moog_configure_step_f4, moog_configure_step_t3,
                                          moog_configure_step_t4, moog_configure_step_m3, moog_configure_step_m4};
     for (int v = 0; v < 6 && err == hipSuccess; ++v) err = (hipError_t)configure[v](e->step_lds);
-    if (err == hipSuccess) err = (hipError_t)moog_configure_step_f2(e->step_lds);
-    {   // MOOG_STEP_PRIO="a,b,c": per mille of the launch order that runs at wave priority 3 / >= 2 / >= 1 ("0": off)
-      const char* pr = getenv("MOOG_STEP_PRIO");
-      int a = 0, b = 0, c = 0;
-      if (pr && sscanf(pr, "%d,%d,%d", &a, &b, &c) >= 1) {
-        if (b < a) b = a;
-        if (c < b) c = b;
-        e->prio_pm[0] = a; e->prio_pm[1] = b; e->prio_pm[2] = c;
-      }
-    }
   }
   {
     const StepVariant sv = step_variant_of(prog);
@@ -891,7 +862,6 @@ static KArgs make_args(moog_engine* e, const void* actions, const moog_inject_t*
   for (int k = 0; k < 2; ++k) { a.pool_f64[k] = e->pool_f64[k]; a.pool_i32[k] = e->pool_i32[k]; }
   a.live_f64 = nullptr; a.live_i32 = nullptr;
   a.late_mask = (mode == MODE_STEP && e->late_reset) ? e->late_mask : nullptr;
-  for (int k = 0; k < 3; ++k) a.prio_t[k] = (int32_t)(((int64_t)e->prio_pm[k] * e->n_envs + 999) / 1000);
   a.rank0 = 0;
   memset(&a.draw, 0, sizeof a.draw);   // (moog_engine_step turns the draw records on)
   a.draw_vinfo = e->d_vinfo;
@@ -906,7 +876,6 @@ static void launch_step(moog_engine* e, hipStream_t s, const KArgs& a) {
     return;
   }
   const bool full = e->maze_kernel && !e->late_reset;
-  if (e->step_wps == 2 && !full && !e->dynamic_rules) { moog_launch_step_f2(e->n_envs, e->step_lds, s, a); return; }
   launch[(full ? 4 : (e->dynamic_rules ? 2 : 0)) + (e->step_wps == 4 ? 1 : 0)](e->n_envs, e->step_lds, s, a);
 }
 
@@ -936,7 +905,7 @@ static bool step_emits_draw(moog_engine* e) {
   // (the emitter's scratch in the step kernel's LDS, emit_draw_record: a torus's nine items per slot must fit behind the vertex offsets)
   const bool scratch_fits = e->mask_setup.ncopy == 1 ||
       4u * (size_t)RM_EMIT_SCRATCH_WORDS(e->mask_setup.slots, e->mask_setup.S, e->mask_setup.ncopy) <= (size_t)CAND_CAP * 2 + 128 + 64 * 8;
-  return e->draw_in_step && e->mask_setup.ok && e->draw && e->pe_ns <= 0 && e->aa <= 1 && scratch_fits;
+  return e->mask_setup.ok && e->draw && e->pe_ns <= 0 && e->aa <= 1 && scratch_fits;
 }
 
 static RArgs raster_args(moog_engine* e, uint8_t* image) {
@@ -961,10 +930,6 @@ static RArgs raster_args(moog_engine* e, uint8_t* image) {
   r.sbg = e->s_bg;
   r.sbg_env_stride = 0; r.env_build = nullptr; r.rgb_override = e->rgb_override;
   r.em = emit_args(e); r.draw_ready = 0; r.env0 = 0;
-  {   // (one resident round: the frames a CU holds at once by LDS and registers, or fewer when asked)
-    const int fit = mask_frames_per_cu(r.ms.lds);
-    r.ms.persist_slots = e->raster_persist > 0 ? e->n_cus * (e->raster_persist < fit ? e->raster_persist : fit) : 0;
-  }
   return r;
 }
 
@@ -1182,7 +1147,6 @@ int moog_engine_set_reset_pool(moog_engine_t* e, int32_t enabled) {
       return fail(MOOG_E_UNSUPPORTED, "the reset pool needs kernels to run beside each other (AMD_SERIALIZE_KERNEL / HIP_LAUNCH_BLOCKING / GPU_MAX_HW_QUEUES=1 / counter collection serialise them)");
   }
   if (!e->pool_ready) {
-    { const char* pd = getenv("MOOG_POOL_DEPTH"); if (pd && atoi(pd) >= 1 && atoi(pd) <= 4) e->pool_depth = atoi(pd); }   // experiments
     const size_t n = (size_t)e->n_envs * e->pool_depth;
     if (!e->pool_state) HIPCHK(hipMalloc(&e->pool_state, sizeof(int32_t) * n));
     if (!e->pool_tag) HIPCHK(hipMalloc(&e->pool_tag, sizeof(int32_t) * n));
@@ -1196,8 +1160,6 @@ int moog_engine_set_reset_pool(moog_engine_t* e, int32_t enabled) {
       const char* hwq = getenv("GPU_MAX_HW_QUEUES");
       const int queues = (hwq && atoi(hwq) > 0) ? atoi(hwq) : 4;
       e->pool_streams = queues - 2 < 1 ? 1 : (queues - 2 > moog_engine::POOL_STREAMS ? moog_engine::POOL_STREAMS : queues - 2);
-      const char* ps = getenv("MOOG_POOL_STREAMS");   // experiments
-      if (ps && atoi(ps) > 0 && atoi(ps) <= moog_engine::POOL_STREAMS) e->pool_streams = atoi(ps);
     }
     for (int k = 0; k < e->pool_streams; ++k)
       if (!e->pool_stream[k]) HIPCHK(hipStreamCreateWithFlags(&e->pool_stream[k], hipStreamNonBlocking));

@@ -1,5 +1,5 @@
 // moog_kernels.h -- the step / reset kernels of the engine (templates and launch arguments), shared by
-// the translation units that instantiate them (moog_step_inst.hip, four times; moog_reset.hip) and by
+// the translation units that instantiate them (moog_step_inst.hip, six times; moog_reset.hip) and by
 // the host side (moog_engine.hip), which only sees the launch functions declared at the bottom.
 #pragma once
 #include "moog_device.h"
@@ -9,14 +9,7 @@
 // env that was expensive lately tends to be expensive again (a pile of sprites in contact) even when one call in between was
 // cheap; with the bare cycle count such an env starts late in the next launch and the launch lasts as long as it does.
 // Measured (profiles/r05_step_experiments.txt 4): headline step launch 610 -> 595 us, config 5 unchanged; fmaxf(now, 0.9 x
-// before) gains as much on the headline and loses 2 % on config 5.  -DMOOG_COST_DECAY=d [-DMOOG_COST_EMA] are the experiment's knobs.
-#if defined(MOOG_COST_DECAY) && defined(MOOG_COST_EMA)
-#define MOOG_COST_OF(now, before) (MOOG_COST_DECAY * (before) + (1.0f - MOOG_COST_DECAY) * (now))
-#elif defined(MOOG_COST_DECAY)
-#define MOOG_COST_OF(now, before) fmaxf((now), MOOG_COST_DECAY * (before))
-#else
-#define MOOG_COST_OF(now, before) moog_cost_ema((now), (before))
-#endif
+// before) gains as much on the headline and loses 2 % on config 5.
 // (a `before` that is not a finite number -- a caller's cost array that was never initialised -- would stay in the average for good)
 static __device__ __forceinline__ float moog_cost_ema(float now, float before) {
   return (before >= 0.f && before < 3.0e38f) ? 0.4f * before + 0.6f * now : now;
@@ -186,8 +179,6 @@ struct KArgs {
   int32_t rank0;         // launch rank of workgroup 0 (0; a launch split by rank was measured in round 5, profiles/r05_step_experiments.txt)
   const uint32_t* draw_vinfo;   // vertex slot -> sprite slot | index within the sprite << 8 (the emitter's)
   RmEmit draw;           // draw.out != null: a step (MODE_STEP) also writes the env's draw record (moog_draw_record.h) for the raster launch behind it
-  int32_t prio_t[3];     // wave priorities by launch rank (with `perm`: descending cost of the previous step): workgroups
-                         // [0, t0) issue at priority 3, [t0, t1) at 2, [t1, t2) at 1, the rest at 0; all zero: off
 };
 
 enum { MODE_STEP = 0, MODE_PHYSICS = 1, MODE_RESET_MASK = 2, MODE_FILL = 3 };
@@ -642,7 +633,6 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
   { PROF_T0; load_record(e, a.H, a.L, gf, gq); PROF_ADD(e, 9); }
   if (e.inj && e.lane == 0) EQ(e)[EL(e).o_rng + 2] = 0;
   wsync();
-#ifndef MOOG_NO_FUSED_RESET   // (A/B builds only: the step path without the sampler compiled in)
   if (a.mode == MODE_STEP && uni(EQ(e)[EL(e).o_reset_next]) == 1) {   // auto-reset (environment.py:100-101)
     int held = 0;
     if (!(DYN && pool_adopt(e, a, env, gf, gq, &held))) {   // (the next episode may be waiting in the reset pool)
@@ -672,10 +662,9 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
     emit_draw_record(e, a, env);   // (before the record's stores: a wave waits once for its stores to drain, at its end)
     store_record(e, a.H, a.L, gf, gq, a.fault_flag);
     if (DYN && held) pool_release(a, env, e.lane);
-    if (a.cost && e.lane == 0) a.cost[env] = MOOG_COST_OF((float)(clock64() - t_sched), a.cost[env]);
+    if (a.cost && e.lane == 0) a.cost[env] = moog_cost_ema((float)(clock64() - t_sched), a.cost[env]);
     return;
   }
-#endif
   { PROF_T0; bbox_build_all(e); PROF_ADD(e, 9); }
   PProg P = as_const_prog(a.P);
   const int K = uni(P->updates_per_env_step);
@@ -734,7 +723,7 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
   SEC(e, SEC_STORE);
   emit_draw_record(e, a, env);   // (before the record's stores: a wave waits once for its stores to drain, at its end)
   store_record(e, a.H, a.L, gf, gq, a.fault_flag);
-  if (a.cost && e.lane == 0) a.cost[env] = MOOG_COST_OF((float)(clock64() - t_sched), a.cost[env]);
+  if (a.cost && e.lane == 0) a.cost[env] = moog_cost_ema((float)(clock64() - t_sched), a.cost[env]);
   if ((a.dbg & 128) && e.lane == 0 && a.discount) {   // profiling aid: cycles and work counters instead of outputs
     a.discount[env] = (double)(clock64() - t_begin);
     if (a.reward) a.reward[env] = (double)(e.n_path + 100000 * e.n_resp) + 1e10 * (double)e.n_disj;
@@ -776,15 +765,6 @@ __global__ __launch_bounds__(MOOG_STEP_THREADS, WPS) void moog_step_kernel(KArgs
     }
   } else if (threadIdx.x >= 64) return;
 #endif
-  // The launch lasts as long as its slowest env, and a wavefront that shares its SIMD with two others issues an
-  // instruction every ~9 cycles instead of every ~5: the envs that were expensive in the previous step (they come first in
-  // the launch order) get the SIMD's issue slots ahead of their neighbours.  A scheduling hint: no result depends on it.
-  if (a.perm && a.prio_t[2] > 0) {
-    const int b = env;
-    if (b < a.prio_t[0]) __builtin_amdgcn_s_setprio(3);
-    else if (b < a.prio_t[1]) __builtin_amdgcn_s_setprio(2);
-    else if (b < a.prio_t[2]) __builtin_amdgcn_s_setprio(1);
-  }
   if (a.perm) env = a.perm[env];
 #ifdef MOOG_SPEC_PROGRAM_INC
   {   // a program-specialised build (moog_step_spec.hip): the layout is a compile-time constant like the program itself
@@ -804,14 +784,12 @@ __global__ __launch_bounds__(MOOG_STEP_THREADS, WPS) void moog_step_kernel(KArgs
 // ---- launch functions (one translation unit each, so that they compile in parallel) ------------------
 // variant = (dynamic rules ? 2 : 0) + (waves per SIMD == 4 ? 1 : 0)
 typedef void (*moog_step_launch_fn)(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
-void moog_launch_step_f2(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 void moog_launch_step_f3(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 void moog_launch_step_f4(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 void moog_launch_step_t3(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 void moog_launch_step_t4(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 void moog_launch_step_m3(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 void moog_launch_step_m4(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
-int moog_configure_step_f2(size_t lds);
 int moog_configure_step_f3(size_t lds);
 int moog_configure_step_f4(size_t lds);
 int moog_configure_step_t3(size_t lds);

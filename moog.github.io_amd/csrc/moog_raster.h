@@ -56,7 +56,6 @@ struct RmSetup {
   uint32_t bg;
   RmPlan plan;
   uint32_t lds;
-  int32_t persist_slots;   // > 0: workgroups resident on the device at once; a launch of more frames is one round of workgroups that draw several frames each
 };
 
 struct RArgs {

@@ -38,7 +38,7 @@ void moog_raster_launch(const RArgs& a, size_t lds_bytes, hipStream_t stream) {
       d.em = a.em; d.P = a.P; d.L = a.L; d.f64 = a.f64; d.i32 = a.i32; d.vinfo = a.vinfo; d.n_envs = a.n_envs; d.env0 = a.env0;
       moog_draw_derive_launch(d, stream);
     }
-    moog_raster_mask_launch(mask_args(a), a.ms.lds, stream, a.ms.persist_slots);
+    moog_raster_mask_launch(mask_args(a), a.ms.lds, stream);
     return;
   }
   const dim3 grid((unsigned)a.n_envs * (unsigned)(a.tiles_x * a.bands));

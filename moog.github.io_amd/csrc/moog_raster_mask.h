@@ -2,9 +2,6 @@
 // moog_raster_mask_core.h with barriers in between.  Included by moog_raster.hip.
 #ifndef MOOG_RASTER_MASK_H_
 #define MOOG_RASTER_MASK_H_
-#ifndef RM_PERSIST
-#define RM_PERSIST 0   // 1: a workgroup may draw several frames one after the other (MOOG_RASTER_PERSIST; measured in round 6: profiles/r06_raster.txt)
-#endif
 #include <hip/hip_runtime.h>
 
 #include "moog_raster_mask_core.h"
@@ -20,16 +17,8 @@ template <int WORDS, bool BIG, bool COMPACT>
 __global__ __launch_bounds__(RM_THREADS, RM_WAVES_PER_SIMD) void moog_raster_mask_kernel(RmArgs a) {
   const RmCtx c = rm_ctx(a.plan, moog_lds);
   const int tid = (int)threadIdx.x, lane = tid & 63;
-  // A workgroup draws the frames blockIdx.x, blockIdx.x + gridDim.x, ... (moog_raster_mask_launch: one frame per workgroup, or
-  // -- MOOG_RASTER_PERSIST -- as many workgroups as are resident at once, each drawing its share one after the other)
-#if RM_PERSIST
-  for (int env = (int)blockIdx.x; env < a.n_envs; env += (int)gridDim.x) {
-  if (env != (int)blockIdx.x) __syncthreads();   // (the tables are the previous frame's until every thread has stored its segments)
-#else
   const int env = (int)blockIdx.x;
   if (env >= a.n_envs) return;
-  {
-#endif
   rm_load(a, c, env, tid, RM_THREADS);
   __syncthreads();
   if (a.debug_stop == 1 || a.debug_stop == 2) return;
@@ -76,7 +65,6 @@ __global__ __launch_bounds__(RM_THREADS, RM_WAVES_PER_SIMD) void moog_raster_mas
     rm_next_pass(a, c, tid, RM_THREADS);
     __syncthreads();
   }
-  }
 }
 
 // The draw records of frames the engine did not step itself (moog_engine_render after load_state or an edit of the state
@@ -113,16 +101,8 @@ static inline int moog_raster_mask_configure(size_t lds_bytes) {
   return (int)err;
 }
 
-static inline void moog_raster_mask_launch(const RmArgs& a, size_t lds_bytes, hipStream_t stream, int persist_slots = 0) {
-  // persist_slots > 0: that many workgroups are resident on the device at once; the launch is cut into equal shares for at most
-  // that many workgroups (4096 frames on 2560 slots: 2048 workgroups of two frames) so that it runs as ONE resident round
-  unsigned g = (unsigned)a.n_envs;
-  if (RM_PERSIST && persist_slots > 0 && a.n_envs > persist_slots) {
-    const int per = (a.n_envs + persist_slots - 1) / persist_slots;
-    g = (unsigned)((a.n_envs + per - 1) / per);
-  }
-  const dim3 grid(g);
-  hipLaunchKernelGGL(moog_raster_mask_pick(a.W > 64 ? 2 : 1, a.big != 0, a.compact != 0), grid, dim3(RM_THREADS), lds_bytes, stream, a);
+static inline void moog_raster_mask_launch(const RmArgs& a, size_t lds_bytes, hipStream_t stream) {
+  hipLaunchKernelGGL(moog_raster_mask_pick(a.W > 64 ? 2 : 1, a.big != 0, a.compact != 0), dim3((unsigned)a.n_envs), dim3(RM_THREADS), lds_bytes, stream, a);
 }
 
 static inline void moog_draw_derive_launch(const RmDeriveArgs& d, hipStream_t stream) {

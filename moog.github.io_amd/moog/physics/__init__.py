@@ -1,7 +1,7 @@
 """Physics components (reference: moog/physics/__init__.py:3-21).
 
 Parameter records only -- the integrators and the collision response run in the
-HIP step kernel (csrc/moog_step.hip).  Constructor signatures follow the
+HIP step kernel (csrc/moog_kernels.h, csrc/moog_device.h).  Constructor signatures follow the
 reference: physics.py:15, collisions.py:466-467, friction.py:20,46,
 gravity.py:13,36, distance_fn_force.py:17,50-53,77, random_force.py:11,
 constant_speed.py:18.

@@ -11,7 +11,7 @@ mkdir -p $B
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -Wno-unused-value "$@" \
   -DMOOG_STEP_DYN=$DYN -DMOOG_STEP_WPS=$WPS -DMOOG_STEP_TAG=$UNIT -c moog.github.io_amd/csrc/moog_step_inst.hip -o $B/step_${UNIT}_$NAME.o 2>&1 | grep -E "error|warning: v"
 OBJS=""
-for u in f2 f3 f4 t3 t4 m3 m4; do
+for u in f3 f4 t3 t4 m3 m4; do
   if [ $u = $UNIT ]; then OBJS="$OBJS $B/step_${UNIT}_$NAME.o"; else OBJS="$OBJS $L/moog_step_$u.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $OBJS $L/moog_reset_r0.o $L/moog_reset_r1.o $L/moog_engine.o $L/moog_raster.o \
