@@ -45,6 +45,7 @@ extern "C" {
 #define MOOG_MAX_ACTIONS 4
 #define MOOG_MAX_MORE_ACTIONS 3 /* MOOG_MAX_ACTIONS - 1 */
 #define MOOG_NUM_FACTORS 14
+#define MOOG_MAX_VIEWS 4     /* PILRenderer observers one engine draws: the program's render + 3 extra views (moog_engine_add_view) */
 #define MOOG_MAX_HDRAWS 32   /* draws a state_initializer takes from np.random directly (per reset) */
 #define MOOG_MAX_OP_DRAWS 24 /* draws of one generation op: its sampled factors + the direct draws made between them */
 
@@ -693,7 +694,10 @@ typedef struct {
 typedef struct moog_engine moog_engine_t;
 
 /* kernel ids for moog_engine_kernel_time() */
-enum { MOOG_K_STEP = 0, MOOG_K_RASTER = 1, MOOG_K_RESET = 2, MOOG_K_COUNT = 3 };
+/* MOOG_K_RASTER: the program's own frames (views[0]); MOOG_K_VIEWS: everything the extra views of moog_engine_add_view cost a
+ * call -- their one derive launch (which also derives the primary's records when a render call needs them) and their raster,
+ * crop and resize launches */
+enum { MOOG_K_STEP = 0, MOOG_K_RASTER = 1, MOOG_K_RESET = 2, MOOG_K_VIEWS = 3, MOOG_K_COUNT = 4 };
 
 int moog_abi_version(void);
 /* The digest of the kernel sources and hipcc flags the library was built from (moog/_digest.py: 64 bits of SHA-256 over
@@ -735,6 +739,21 @@ int moog_engine_physics_only(moog_engine_t* e, const moog_inject_t* inject,
                              void* hip_stream);
 /* env.observation() only (environment.py:128-131, runtime_benchmark.py:113-130). */
 int moog_engine_render(moog_engine_t* e, uint8_t* image_dev, void* hip_stream);
+
+/* Extra views (environment.py:128-131 returns {key: observer(state)} for every observer of the config: a config may hold
+ * several PILRenderers).  The program's `render` is view 0, the primary; moog_engine_add_view adds another renderer of the
+ * same state -- its own size, anti-aliasing, colour map, polygon modifier and background -- and returns its index (1 ..
+ * MOOG_MAX_VIEWS - 1) in *view.  Views belong to the engine handle, never to the program (its bytes and hash stay those of
+ * the config's first renderer).  moog_engine_set_view_image binds the device buffer [n_envs][height][width][3] that view's
+ * frames go to (NULL unbinds).  Every call that draws the primary's frames (moog_engine_reset / moog_engine_step with
+ * out->image, moog_engine_render) also draws every extra view that has a bound buffer.  Extra views draw every sprite (no
+ * per-env prefix picture); a colour override (moog_engine_set_color_override) applies to every view.
+ * moog_engine_view_raster_path: moog_engine_raster_path of one view (0 = the primary).
+ * A program whose render is 0 x 0 draws no frames: its engine has no raster state, takes no views, and a reset / step /
+ * render handed an image fails with MOOG_E_INVALID. */
+int moog_engine_add_view(moog_engine_t* e, const moog_render_t* render, int32_t* view);
+int moog_engine_set_view_image(moog_engine_t* e, int32_t view, uint8_t* image_dev);
+int moog_engine_view_raster_path(moog_engine_t* e, int32_t view, int32_t* path);
 
 /* Optional launch-order schedule for the step kernel (pure performance hint, results do
  * not depend on it).  `cost_dev` (float[n_envs], borrowed; zeroed by this call) holds a moving average of every env's

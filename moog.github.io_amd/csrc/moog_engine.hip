@@ -27,6 +27,7 @@
 // host side: engine object + C ABI
 // =====================================================================================
 static thread_local std::string g_err;
+static const char* const FRAMELESS_MSG = "this program draws no frames (no PILRenderer observer: render 0 x 0): pass no image";
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #define HIPCHK(x)                                                                        \
   do {                                                                                   \
@@ -42,6 +43,37 @@ struct TimedKernel {
   int64_t seq = 0;   // launches seen while timing is on (every `period`-th one is bracketed)
 };
 
+// Everything the engine holds per render configuration: views[0] draws the program's `render` (the primary: the config's first
+// PILRenderer), views[1 ..] the extra renderers of moog_engine_add_view.  Shared between views, in moog_engine: the static
+// prefix's scratch record (s_f64 / s_i32: a reset does not depend on the renderer), the anti-aliasing scratch canvas (launches
+// on a stream are serial) and the per-env prefix (the primary's only).
+struct RView {
+  moog_render_t render{};
+  const moog_program_t* P = nullptr;   // the device program the span kernel reads `render` from: the engine's for the primary,
+  moog_program_t* d_own = nullptr;     // for an extra view a copy of it with `render` replaced (d_own)
+  uint8_t* image = nullptr;            // an extra view's bound frames (moog_engine_set_view_image), or null
+  RPlan raster_plan_{};
+  RmSetup mask_setup{};   // the mask rasteriser (moog_raster_mask_core.h): ok = this view's ordinary frames are drawn by it
+  uint8_t* draw = nullptr;        // its input: a draw record per env (moog_draw_record.h), written by the step kernel or derived before the launch
+  RmDrawLayout draw_lay{};
+  int raster_tile_w = 0, raster_band_h = 0, raster_tiles_x = 1, raster_bands = 1;   // one workgroup per tile of the canvas
+  // anti_aliasing > 1: frames are drawn on a canvas aa x the observation (a chunk of envs at a time) and down-sampled
+  int aa = 1, canvas_w = 0, canvas_h = 0, aa_chunk = 0;
+  int pad_w = 0;                  // canvas_w rounded up to a multiple of 16: the width the rasteriser draws (pil_renderer.py:64-66
+                                  // accepts any size; the extra columns are what Pillow would draw on a wider image, and are dropped)
+  uint8_t* pad_img = nullptr;     // [n_envs][canvas_h][pad_w][3] when pad_w != canvas_w without anti-aliasing (cropped into the caller's frames)
+  int32_t* aa_tables = nullptr;   // bounds + coefficients of both axes
+  RResize aa_resize{};
+  int raster_chunk = 0, raster_words = 0, raster_iwords = 0, raster_hwords = 1, raster_xxcap = 4;
+  size_t raster_lds = 0;
+  int32_t* rows_seen = nullptr;    // two pinned host words: the most polygon rows a frame wanted when that was more than the mask rasteriser's row records; how many frames did
+  int raster_rows_fixed = 0;       // MOOG_RASTER_ROWS pins the records (tests of the multi-pass path)
+  int mask_free_cap = 0;           // the most row records that cost no resident frame per CU (mask_free_rows)
+  // static prefix of the rasteriser (moog_raster.h): the reference sprites (moog_engine::s_f64 / s_i32) and their picture
+  int n_static = 0, nsv = 0, kept_n_static = 0;   // (kept: while a colour override has the prefix switched off)
+  uint8_t* s_bg = nullptr;
+};
+
 struct moog_engine {
   moog_program_t prog;
   moog_layout_t L;
@@ -53,7 +85,7 @@ struct moog_engine {
   uint64_t seed = 0;
   int64_t env_index0 = 0;
   moog_state_view_t view{nullptr, nullptr};
-  size_t step_lds = 0, raster_lds = 0;
+  size_t step_lds = 0;
   int step_wps = 4;   // register-allocation variant of the step kernel (waves per SIMD)
   void* spec_handle = nullptr;   // a step kernel compiled for this very program (load_spec_kernel), or null
   void (*spec_launch)(int, size_t, hipStream_t, const KArgs*) = nullptr;
@@ -67,21 +99,12 @@ struct moog_engine {
   bool late_reset = false;    // ... but only to build an episode: it is stepped by the kernels without the rare components, and
                               // the full reset kernel behind every step launch opens the episodes those could not (step_env)
   uint8_t* late_mask = nullptr;   // [n_envs]
-  RPlan raster_plan_{};
-  RmSetup mask_setup{};   // the mask rasteriser (moog_raster_mask_core.h): ok = this program's ordinary frames are drawn by it
-  uint8_t* draw = nullptr;        // its input: a draw record per env (moog_draw_record.h), written by the step kernel or derived before the launch
-  RmDrawLayout draw_lay{};
-  int raster_tile_w = 0, raster_band_h = 0, raster_tiles_x = 1, raster_bands = 1;   // one workgroup per tile of the canvas
-  // anti_aliasing > 1: frames are drawn on a canvas aa x the observation (a chunk of envs at a time) and down-sampled
-  int aa = 1, canvas_w = 0, canvas_h = 0, aa_chunk = 0;
-  int pad_w = 0;                  // canvas_w rounded up to a multiple of 16: the width the rasteriser draws (pil_renderer.py:64-66
-                                  // accepts any size; the extra columns are what Pillow would draw on a wider image, and are dropped)
-  uint8_t* pad_img = nullptr;     // [n_envs][canvas_h][pad_w][3] when pad_w != canvas_w without anti-aliasing (cropped into the caller's frames)
-  uint8_t* aa_canvas = nullptr;   // [aa_chunk][canvas_h][pad_w][3]
+  RView views[MOOG_MAX_VIEWS];
+  int n_views = 1;               // views[0] and the extra views added so far
+  bool frameless = false;        // render 0 x 0: the program draws no frames (no raster state at all)
+  uint8_t* aa_canvas = nullptr;   // shared by the anti-aliased views: [aa_chunk][canvas_h][pad_w][3] of whichever is drawn
   uint8_t* aa_tmp = nullptr;      // [aa_chunk][canvas_h][width rounded up to 4][3]
-  int32_t* aa_tables = nullptr;   // bounds + coefficients of both axes
-  RResize aa_resize{};
-  int raster_chunk = 0, raster_words = 0, raster_iwords = 0, raster_hwords = 1, raster_xxcap = 4;
+  size_t aa_canvas_bytes = 0, aa_tmp_bytes = 0;
   int timing = 0;   // bit k: launches of kernel k are bracketed by HIP events
   int32_t* perm = nullptr;
   hipStream_t sched_stream = nullptr;   // the launch-order sort runs beside the rasteriser
@@ -106,18 +129,13 @@ struct moog_engine {
   int32_t* layer_hw = nullptr;   // [2 * MOOG_MAX_LAYERS]: high-water mark / dropped appends of the dynamic layers
   TimedKernel timed[MOOG_K_COUNT];
   int32_t* fault_flag = nullptr;   // pinned host word the kernels OR fault bits into
-  int32_t* rows_seen = nullptr;    // two pinned host words: the most polygon rows a frame wanted when that was more than the mask rasteriser's row records; how many frames did
-  int raster_rows_fixed = 0;       // MOOG_RASTER_ROWS pins the records (tests of the multi-pass path)
-  int mask_free_cap = 0;           // the most row records that cost no resident frame per CU (mask_free_rows)
   int step_dbg = 0, raster_stop = 0;   // profiling aids (MOOG_STEP_DEBUG / MOOG_RASTER_STOP at create, moog_engine_set_debug)
   // static prefix of the rasteriser (moog_raster.h): a scratch env record that holds the reference
   // sprites (what a reset makes of the constant generation ops) and their picture
-  int n_static = 0, nsv = 0;
   double* s_f64 = nullptr;
   int32_t* s_i32 = nullptr;
-  uint8_t* s_bg = nullptr;
   const uint32_t* rgb_override = nullptr;   // moog_engine_set_color_override
-  int kept_n_static = 0, kept_pe_ns = 0, kept_pe_nsv = 0;   // the prefixes' sizes while a colour override has them switched off
+  int kept_pe_ns = 0, kept_pe_nsv = 0;   // the prefixes' sizes while a colour override has them switched off
   // per-env prefix (RArgs::sbg_env_stride): leading sprites that stay put within an episode but differ between envs
   int pe_ns = 0, pe_nsv = 0;        // slots / vertex slots of the prefix (0: off); shrinks to the slots that really stay put
   double* pe_f64 = nullptr;         // [n_envs] snapshot of the record each env's picture was drawn from
@@ -132,16 +150,19 @@ static void free_engine(moog_engine* e) {
   if (e->d_prog) hipFree(e->d_prog);
   if (e->d_vslot) hipFree(e->d_vslot);
   if (e->d_vinfo) hipFree(e->d_vinfo);
-  if (e->draw) hipFree(e->draw);
+  for (RView& v : e->views) {
+    if (v.d_own) hipFree(v.d_own);
+    if (v.draw) hipFree(v.draw);
+    if (v.s_bg) hipFree(v.s_bg);
+    if (v.pad_img) hipFree(v.pad_img);
+    if (v.aa_tables) hipFree(v.aa_tables);
+    if (v.rows_seen) hipHostFree(v.rows_seen);
+  }
   if (e->s_f64) hipFree(e->s_f64);
   if (e->s_i32) hipFree(e->s_i32);
-  if (e->s_bg) hipFree(e->s_bg);
   if (e->aa_canvas) hipFree(e->aa_canvas);
-  if (e->pad_img) hipFree(e->pad_img);
   if (e->aa_tmp) hipFree(e->aa_tmp);
-  if (e->aa_tables) hipFree(e->aa_tables);
   if (e->fault_flag) hipHostFree(e->fault_flag);
-  if (e->rows_seen) hipHostFree(e->rows_seen);
   if (e->layer_hw) hipFree(e->layer_hw);
   for (int k = 0; k < moog_engine::POOL_STREAMS; ++k)
     if (e->pool_stream[k]) { hipStreamSynchronize(e->pool_stream[k]); hipStreamDestroy(e->pool_stream[k]); }
@@ -166,9 +187,9 @@ static void free_engine(moog_engine* e) {
 // Leading sprite slots that every reset creates identically and at rest: slots filled by generation
 // ops without a random factor, zero velocity.  Whether a frame's prefix really equals the reference
 // is checked by the raster kernel per frame, so this only has to be a good guess.
-static int static_prefix_slots(const moog_program_t* p, int* nsv) {
+static int static_prefix_slots(const moog_program_t* p, int polymod, int* nsv) {
   *nsv = 0;
-  if (p->render.polymod != MOOG_POLYMOD_NONE) return 0;
+  if (polymod != MOOG_POLYMOD_NONE) return 0;
   std::vector<char> ok((size_t)(p->n_slots > 0 ? p->n_slots : 1), 0);
   for (int oi = 0; oi < p->n_ops; ++oi) {
     const moog_genop_t& op = p->ops[oi];
@@ -328,6 +349,19 @@ unsigned long long moog_source_digest(void) { return MOOG_SRC_DIGEST; }
 const char* moog_last_error(void) { return g_err.c_str(); }
 int64_t moog_program_sizeof(void) { return (int64_t)sizeof(moog_program_t); }
 
+static int validate_render(const moog_program_t* p, const moog_render_t* r) {
+  const int aa = r->aa > 1 ? r->aa : 1;
+  const long long cw = (long long)aa * r->width, ch = (long long)aa * r->height;
+  if (cw < 1 || cw > 8192 || ch < 1 || ch > 8192 || aa > 16)
+    return fail(MOOG_E_UNSUPPORTED, "render size unsupported (1 <= anti_aliasing x width, height <= 8192, anti_aliasing <= 16)");
+  if (r->cmap != MOOG_CMAP_IDENTITY && r->cmap != MOOG_CMAP_HSV) return fail(MOOG_E_INVALID, "render cmap out of range");
+  if (r->polymod != MOOG_POLYMOD_NONE && r->polymod != MOOG_POLYMOD_TORUS && r->polymod != MOOG_POLYMOD_FIRST_PERSON)
+    return fail(MOOG_E_INVALID, "render polymod out of range");
+  if (r->polymod == MOOG_POLYMOD_FIRST_PERSON && (r->polymod_layer < 0 || r->polymod_layer >= p->n_layers))
+    return fail(MOOG_E_INVALID, "render polymod_layer out of range");
+  return MOOG_OK;
+}
+
 static int validate(const moog_program_t* p) {
   if (!p) return fail(MOOG_E_INVALID, "null program");
   if (p->abi_version != MOOG_ABI_VERSION) return fail(MOOG_E_INVALID, "program abi_version mismatch");
@@ -349,18 +383,16 @@ static int validate(const moog_program_t* p) {
   if (p->maze.random && (p->maze.gen_size < 1 || p->maze.gen_size > MOOG_MAX_MAZE_GEN || p->maze.size < p->maze.gen_size ||
                          p->maze.size > MOOG_MAX_MAZE))
     return fail(MOOG_E_UNSUPPORTED, "random maze size unsupported");
-  {
-    const int aa = p->render.aa > 1 ? p->render.aa : 1;
-    const long long cw = (long long)aa * p->render.width, ch = (long long)aa * p->render.height;
-    if (cw < 1 || cw > 8192 || ch < 1 || ch > 8192 || aa > 16)
-      return fail(MOOG_E_UNSUPPORTED, "render size unsupported (1 <= anti_aliasing x width, height <= 8192, anti_aliasing <= 16)");
+  if (!(p->render.width == 0 && p->render.height == 0)) {   // (0 x 0: the program draws no frames)
+    const int rc = validate_render(p, &p->render);
+    if (rc) return rc;
   }
   return MOOG_OK;
 }
 
 static KArgs make_args(moog_engine* e, const void* actions, const moog_inject_t* inj,
                        const moog_step_out_t* out, int mode, const uint8_t* mask);
-static RArgs raster_args(moog_engine* e, uint8_t* image);
+static RArgs raster_args(moog_engine* e, RView& v, uint8_t* image);
 
 // Pillow Resample.c precompute_coeffs + normalize_coeffs_8bpc for the LANCZOS filter (support 3): the window of
 // output sample xx is centred on (xx + 0.5) * scale, weights are normalised in double and rounded to fixed
@@ -400,14 +432,14 @@ static int resize_coeffs(int in_size, int out_size, std::vector<int32_t>& bounds
   return ksize;
 }
 
-static int setup_anti_aliasing(moog_engine* e) {
-  if (e->aa <= 1) return MOOG_OK;
-  const int ow = e->prog.render.width, oh = e->prog.render.height;
+static int setup_anti_aliasing(moog_engine* e, RView& v) {
+  if (v.aa <= 1) return MOOG_OK;
+  const int ow = v.render.width, oh = v.render.height;
   std::vector<int32_t> bh, bv, ch, cv;
-  const int kh = resize_coeffs(e->canvas_w, ow, bh, ch), kv = resize_coeffs(e->canvas_h, oh, bv, cv);
+  const int kh = resize_coeffs(v.canvas_w, ow, bh, ch), kv = resize_coeffs(v.canvas_h, oh, bv, cv);
   const size_t words = bh.size() + bv.size() + ch.size() + cv.size();
-  if (hipMalloc(&e->aa_tables, words * sizeof(int32_t)) != hipSuccess) return fail(MOOG_E_NOMEM, "hipMalloc(resize tables) failed");
-  int32_t* d = e->aa_tables;
+  if (hipMalloc(&v.aa_tables, words * sizeof(int32_t)) != hipSuccess) return fail(MOOG_E_NOMEM, "hipMalloc(resize tables) failed");
+  int32_t* d = v.aa_tables;
   HIPCHK(hipMemcpy(d, bh.data(), bh.size() * 4, hipMemcpyHostToDevice)); const int32_t* dbh = d; d += bh.size();
   HIPCHK(hipMemcpy(d, bv.data(), bv.size() * 4, hipMemcpyHostToDevice)); const int32_t* dbv = d; d += bv.size();
   HIPCHK(hipMemcpy(d, ch.data(), ch.size() * 4, hipMemcpyHostToDevice)); const int32_t* dch = d; d += ch.size();
@@ -420,46 +452,65 @@ static int setup_anti_aliasing(moog_engine* e) {
   }
   hspan = (hspan + 7) & ~3;
   const int tstride = (ow + 3) & ~3;
-  e->aa_resize = RResize{e->canvas_w, e->canvas_h, ow, oh, kh, kv, dbh, dbv, dch, dcv, hspan, e->pad_w, tstride};
-  // canvases of a chunk of envs at a time: at most 1 GiB of scratch
-  const size_t canvas = (size_t)e->pad_w * e->canvas_h * 3;
+  v.aa_resize = RResize{v.canvas_w, v.canvas_h, ow, oh, kh, kv, dbh, dbv, dch, dcv, hspan, v.pad_w, tstride};
+  // canvases of a chunk of envs at a time: at most 1 GiB of scratch, one scratch for every view (launches on a stream are
+  // serial): it grows to the largest view's
+  const size_t canvas = (size_t)v.pad_w * v.canvas_h * 3;
   size_t chunk = ((size_t)1 << 30) / canvas;
   if (chunk < 1) chunk = 1;
   if (chunk > (size_t)e->n_envs) chunk = (size_t)e->n_envs;
-  e->aa_chunk = (int)chunk;
-  if (hipMalloc(&e->aa_canvas, chunk * canvas) != hipSuccess ||
-      hipMalloc(&e->aa_tmp, chunk * (size_t)e->canvas_h * tstride * 3) != hipSuccess)
-    return fail(MOOG_E_NOMEM, "hipMalloc(anti-aliasing canvas) failed");
+  v.aa_chunk = (int)chunk;
+  const size_t cb = chunk * canvas, tb = chunk * (size_t)v.canvas_h * tstride * 3;
+  if (cb > e->aa_canvas_bytes || tb > e->aa_tmp_bytes) {
+    if (e->aa_canvas || e->aa_tmp) HIPCHK(hipDeviceSynchronize());   // (an earlier call's launches may still use the old scratch)
+    if (cb > e->aa_canvas_bytes) {
+      if (e->aa_canvas) hipFree(e->aa_canvas);
+      e->aa_canvas = nullptr; e->aa_canvas_bytes = 0;
+      if (hipMalloc(&e->aa_canvas, cb) != hipSuccess) return fail(MOOG_E_NOMEM, "hipMalloc(anti-aliasing canvas) failed");
+      e->aa_canvas_bytes = cb;
+    }
+    if (tb > e->aa_tmp_bytes) {
+      if (e->aa_tmp) hipFree(e->aa_tmp);
+      e->aa_tmp = nullptr; e->aa_tmp_bytes = 0;
+      if (hipMalloc(&e->aa_tmp, tb) != hipSuccess) return fail(MOOG_E_NOMEM, "hipMalloc(anti-aliasing canvas) failed");
+      e->aa_tmp_bytes = tb;
+    }
+  }
   return MOOG_OK;
 }
 
 // Resets one scratch env (the constant generation ops do not depend on the random stream) and renders
 // its static prefix on top of the background colour: the reference record and picture of moog_raster.h.
-static int build_static_prefix(moog_engine* e) {
+// The scratch record is the same for every view (a reset does not depend on the renderer): made once, by the first view
+// that has a prefix; each view draws its own picture from it.
+static int build_static_prefix(moog_engine* e, RView& v) {
   int nsv = 0;
-  const int ns = getenv("MOOG_RASTER_NO_STATIC") ? 0 : static_prefix_slots(&e->prog, &nsv);
+  const int ns = getenv("MOOG_RASTER_NO_STATIC") ? 0 : static_prefix_slots(&e->prog, v.render.polymod, &nsv);
   if (ns == 0) return MOOG_OK;
-  const size_t fb = (size_t)e->L.f64_per_env * 8, ib = (size_t)e->L.i32_per_env * 4;
-  const size_t pb = (size_t)e->pad_w * e->canvas_h * 3;
-  if (hipMalloc(&e->s_f64, fb) != hipSuccess || hipMalloc(&e->s_i32, ib) != hipSuccess ||
-      hipMalloc(&e->s_bg, pb) != hipSuccess)
-    return fail(MOOG_E_NOMEM, "hipMalloc(static prefix) failed");
-  HIPCHK(hipMemset(e->s_f64, 0, fb));
-  HIPCHK(hipMemset(e->s_i32, 0, ib));
+  const size_t pb = (size_t)v.pad_w * v.canvas_h * 3;
+  if (hipMalloc(&v.s_bg, pb) != hipSuccess) return fail(MOOG_E_NOMEM, "hipMalloc(static prefix) failed");
   const moog_state_view_t keep = e->view;
   const int32_t keep_n = e->n_envs;
+  if (!e->s_f64) {
+    const size_t fb = (size_t)e->L.f64_per_env * 8, ib = (size_t)e->L.i32_per_env * 4;
+    if (hipMalloc(&e->s_f64, fb) != hipSuccess || hipMalloc(&e->s_i32, ib) != hipSuccess)
+      return fail(MOOG_E_NOMEM, "hipMalloc(static prefix) failed");
+    HIPCHK(hipMemset(e->s_f64, 0, fb));
+    HIPCHK(hipMemset(e->s_i32, 0, ib));
+    e->view.f64 = e->s_f64; e->view.i32 = e->s_i32; e->n_envs = 1;
+    KArgs a = make_args(e, nullptr, nullptr, nullptr, MODE_RESET_MASK, nullptr);
+    a.dbg = 0;
+    a.fault_flag = nullptr;   // (faults of the scratch env are nobody's business)
+    (e->maze_kernel ? moog_launch_reset_full : moog_launch_reset_plain)(1, e->step_lds, 0, a);
+  }
   e->view.f64 = e->s_f64; e->view.i32 = e->s_i32; e->n_envs = 1;
-  KArgs a = make_args(e, nullptr, nullptr, nullptr, MODE_RESET_MASK, nullptr);
-  a.dbg = 0;
-  a.fault_flag = nullptr;   // (faults of the scratch env are nobody's business)
-  (e->maze_kernel ? moog_launch_reset_full : moog_launch_reset_plain)(1, e->step_lds, 0, a);
-  RArgs r = raster_args(e, e->s_bg);
+  RArgs r = raster_args(e, v, v.s_bg);
   r.n_static = ns; r.nsv = nsv; r.build = 1; r.debug_stop = 0;
-  moog_raster_launch(r, e->raster_lds, 0);
+  moog_raster_launch(r, v.raster_lds, 0);
   e->view = keep; e->n_envs = keep_n;
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(0));
-  e->n_static = ns; e->nsv = nsv;
+  v.n_static = ns; v.nsv = nsv;
   return MOOG_OK;
 }
 
@@ -471,15 +522,15 @@ static int build_static_prefix(moog_engine* e) {
 // The mask rasteriser's row records per pass (moog_raster_mask_core.h): `cap` of them, at least a canvas height so that any one
 // polygon fits, at most one per (polygon, canvas row) and 4096 (the row sort's 12-bit places), and no more than 64 KB of LDS
 // leave room for.  ok = 0 when even the smallest plan does not fit.
-static void mask_plan_rows(moog_engine* e, int cap) {
-  RmSetup& ms = e->mask_setup;
+static void mask_plan_rows(moog_engine* e, RView& v, int cap) {
+  RmSetup& ms = v.mask_setup;
   if (cap > 4096) cap = 4096;
-  if (cap > ms.S * e->canvas_h) cap = ms.S * e->canvas_h;
-  if (cap < e->canvas_h) cap = e->canvas_h;
+  if (cap > ms.S * v.canvas_h) cap = ms.S * v.canvas_h;
+  if (cap < v.canvas_h) cap = v.canvas_h;
   for (;;) {
-    rm_plan(ms.S, e->L.TOTV * ms.ncopy, e->pad_w, e->canvas_h, cap, ms.iwords, RM_THREADS / 64, ms.big, &ms.plan, ms.compact);
-    if (ms.plan.total <= 64u * 1024u || cap <= e->canvas_h) break;
-    cap = cap - 64 > e->canvas_h ? cap - 64 : e->canvas_h;
+    rm_plan(ms.S, e->L.TOTV * ms.ncopy, v.pad_w, v.canvas_h, cap, ms.iwords, RM_THREADS / 64, ms.big, &ms.plan, ms.compact);
+    if (ms.plan.total <= 64u * 1024u || cap <= v.canvas_h) break;
+    cap = cap - 64 > v.canvas_h ? cap - 64 : v.canvas_h;
   }
   ms.cap_rows = cap;
   ms.lds = ms.plan.total;
@@ -498,40 +549,41 @@ static int mask_frames_per_cu(uint32_t lds) {   // by LDS, and by registers: RM_
   return n > by_regs ? by_regs : n;
 }
 // the most row records that cost no resident frame per CU against the plan in hand (called once, at create)
-static int mask_free_rows(moog_engine* e) {
-  RmSetup& ms = e->mask_setup;
+static int mask_free_rows(moog_engine* e, RView& v) {
+  RmSetup& ms = v.mask_setup;
   const RmSetup first = ms;
   int best = first.cap_rows;
   for (int cap = first.cap_rows + 32; cap <= 4096; cap += 32) {
     ms = first;
-    mask_plan_rows(e, cap);
+    mask_plan_rows(e, v, cap);
     if (!ms.ok || ms.cap_rows < cap || mask_frames_per_cu(ms.lds) < mask_frames_per_cu(first.lds)) break;
     best = cap;
   }
   ms = first;
   return best;
 }
-static void mask_rows_grow(moog_engine* e) {
-  if (!e->rows_seen || e->raster_rows_fixed || e->mask_setup.cap_rows >= e->mask_free_cap) return;
-  const int want = __atomic_load_n(&e->rows_seen[0], __ATOMIC_RELAXED);
-  RmSetup& ms = e->mask_setup;
+static void mask_rows_grow(moog_engine* e, RView& v) {
+  if (!v.rows_seen || v.raster_rows_fixed || v.mask_setup.cap_rows >= v.mask_free_cap) return;
+  const int want = __atomic_load_n(&v.rows_seen[0], __ATOMIC_RELAXED);
+  RmSetup& ms = v.mask_setup;
   if (want <= ms.cap_rows) return;
   const RmSetup before = ms;
   int cap = (want + want / 8 + 31) & ~31;
-  if (cap > e->mask_free_cap) cap = e->mask_free_cap;
-  mask_plan_rows(e, cap);
+  if (cap > v.mask_free_cap) cap = v.mask_free_cap;
+  mask_plan_rows(e, v, cap);
   if (!ms.ok || ms.cap_rows <= before.cap_rows) ms = before;
 }
 
 static int setup_env_prefix(moog_engine* e) {
+  const RView& v = e->views[0];
   const char* sw = getenv("MOOG_RASTER_ENV_BG");
-  if ((sw && atoi(sw) == 0) || e->aa > 1) return MOOG_OK;
+  if ((sw && atoi(sw) == 0) || v.aa > 1) return MOOG_OK;
   const bool forced = sw && atoi(sw) == 1;
   int nsv = 0;
   const int ns = env_prefix_slots(&e->prog, &nsv);
-  const size_t frame = (size_t)e->canvas_h * e->pad_w * 3;
-  if (ns < 16 || ns < e->n_static + 8 || (size_t)e->n_envs * frame > ((size_t)4 << 30)) return MOOG_OK;
-  if (!forced && (e->raster_tiles_x * e->raster_bands < 2 || ns < 32)) return MOOG_OK;
+  const size_t frame = (size_t)v.canvas_h * v.pad_w * 3;
+  if (ns < 16 || ns < v.n_static + 8 || (size_t)e->n_envs * frame > ((size_t)4 << 30)) return MOOG_OK;
+  if (!forced && (v.raster_tiles_x * v.raster_bands < 2 || ns < 32)) return MOOG_OK;
   const size_t n = (size_t)e->n_envs;
   if (hipMalloc(&e->pe_f64, n * e->L.f64_per_env * 8) != hipSuccess || hipMalloc(&e->pe_i32, n * e->L.i32_per_env * 4) != hipSuccess ||
       hipMalloc(&e->pe_bg, n * frame) != hipSuccess || hipMalloc(&e->pe_valid, n * 4) != hipSuccess ||
@@ -546,6 +598,124 @@ static int setup_env_prefix(moog_engine* e) {
   return MOOG_OK;
 }
 
+// The raster state of one view (a render configuration over this engine's program): canvas and tile geometry, the span
+// kernel's LDS plan, the mask rasteriser's setup and its draw records.  The per-env prefix is the primary's only.
+static int setup_view(moog_engine* e, RView& v, bool primary) {
+  const moog_program_t* prog = &e->prog;
+  // raster LDS plan (moog_raster.h): row records for `chunk` rows per pass
+  {
+    // Tiles: the row masks of the kernel are 128 bits, so a wider canvas is cut into columns of the widest
+    // multiple of 16 <= 128 that divides the width, and a taller one into bands of 64 rows.
+    v.aa = v.render.aa > 1 ? v.render.aa : 1;
+    v.canvas_w = v.aa * v.render.width;
+    v.canvas_h = v.aa * v.render.height;
+    v.pad_w = (v.canvas_w + 15) & ~15;
+    int tw = v.pad_w <= 128 ? v.pad_w : 128;
+    while (v.pad_w % tw != 0) tw -= 16;
+    v.raster_tile_w = tw;
+    v.raster_tiles_x = v.pad_w / tw;
+    v.raster_band_h = v.canvas_h <= 128 ? v.canvas_h : 64;
+    {   // (the primary's only: extra views never use the per-env prefix)
+        // frames that will use the per-env prefix (setup_env_prefix): few sprites are left to draw per tile and the per-tile fixed
+        // cost dominates -- whole-height tiles measured 1.65 against 1.73 ms per 4096 pacman frames (profiles/r04_env_prefix.txt)
+        // (decided here, from what the PROGRAM allows: the tile plan sizes every LDS table.  A handle that later runs without the prefix --
+        //  allocation failure, a prefix that shrank to nothing, a colour override -- keeps the whole-height tiles: 1.65 ms against 1.73 ms
+        //  with 64-row bands WITH the prefix, 2.45 against 2.51 ms WITHOUT it in the same file: not a loss either way)
+      int nsv_ = 0;
+      const char* sw = getenv("MOOG_RASTER_ENV_BG");
+      if (primary && v.canvas_h > 128 && v.canvas_h <= 256 && v.aa <= 1 && !(sw && atoi(sw) == 0) && env_prefix_slots(prog, &nsv_) >= 32)
+        v.raster_band_h = v.canvas_h;
+    }
+    v.raster_bands = (v.canvas_h + v.raster_band_h - 1) / v.raster_band_h;
+    int W = v.raster_tile_w, H = v.raster_band_h;   // (the LDS plan is per tile)
+    int ncopy = v.render.polymod == MOOG_POLYMOD_TORUS ? 9 : 1;
+    int items = prog->n_slots * ncopy;
+    if (items < 1) items = 1;
+    v.raster_words = (W + 63) / 64;
+    v.raster_iwords = (items + 31) / 32;
+    int maxv = 2;
+    for (int sl = 0; sl < prog->n_slots; ++sl) if (prog->slot_vcap[sl] > maxv) maxv = prog->slot_vcap[sl];
+    v.raster_xxcap = 2 * maxv;
+    v.raster_hwords = (maxv + 31) / 32;
+    RPlan pl;
+    // Row records per pass: 376 (>= H so that any item fits; sized so that six workgroups of the
+    // 4096 x 32-sprite workload share a CU), then as many more as fit without costing a resident
+    // workgroup (frames with more rows than records take several passes).
+    int cap = items * H;
+    if (cap > 376) cap = 376;
+    if (cap < H) cap = H;
+    raster_plan(prog->n_slots, e->L.TOTV, ncopy, W, H, cap, v.raster_iwords, v.raster_hwords, v.raster_xxcap, &pl);
+    {
+      const unsigned lds_cu = 160 * 1024;
+      unsigned wgs = pl.total ? lds_cu / pl.total : 0;
+      if (wgs > 6) wgs = 6;   // registers hold six workgroups per CU at most
+      const int want = items * H < 4096 ? items * H : 4096;
+      while (wgs && cap < want) {
+        RPlan p2;
+        int c2 = cap + 32 < want ? cap + 32 : want;
+        raster_plan(prog->n_slots, e->L.TOTV, ncopy, W, H, c2, v.raster_iwords, v.raster_hwords, v.raster_xxcap, &p2);
+        if (lds_cu / p2.total < wgs) break;
+        cap = c2; pl = p2;
+      }
+    }
+    { const char* rc = getenv("MOOG_RASTER_ROWS"); if (rc && atoi(rc) >= H) cap = atoi(rc); }   // tuning / tests of the multi-pass path
+    raster_plan(prog->n_slots, e->L.TOTV, ncopy, W, H, cap, v.raster_iwords, v.raster_hwords, v.raster_xxcap, &pl);
+    if (pl.total > 160 * 1024 || (size_t)e->L.TOTV * ncopy >= (1u << 20)) {
+      return fail(MOOG_E_UNSUPPORTED, "raster working set does not fit in LDS");
+    }
+    v.raster_chunk = cap;
+    v.raster_plan_ = pl;
+    v.raster_lds = pl.total;
+  }
+  {   // mask rasteriser (moog_raster_mask_core.h): one-tile frames, polygons of <= 128 vertices, at most 256 polygons (a torus has nine per sprite)
+    RmSetup& ms = v.mask_setup;
+    memset(&ms, 0, sizeof ms);
+    int maxv = 1;
+    for (int sl = 0; sl < prog->n_slots; ++sl) if (prog->slot_vcap[sl] > maxv) maxv = prog->slot_vcap[sl];
+    const int ncopy = v.render.polymod == MOOG_POLYMOD_TORUS ? 9 : 1;
+    const char* sw = getenv("MOOG_RASTER_MASK");   // 0: the push / sort / span kernel for every frame (A/B runs, tests)
+    ms.ok = !(sw && atoi(sw) == 0) && v.raster_tiles_x * v.raster_bands == 1 && v.pad_w <= 128 && v.canvas_h <= 128 &&
+            maxv <= RM_BIG_NV && prog->n_slots >= 1 && prog->n_slots * ncopy <= 256 && e->L.TOTV >= 1;
+    if (ms.ok) {
+      ms.slots = prog->n_slots; ms.ncopy = ncopy; ms.big = maxv > RM_MAX_NV ? 1 : 0;
+      ms.S = prog->n_slots * ncopy;
+      ms.iwords = (ms.S + 31) / 32;
+      ms.cmap = v.render.cmap;
+      ms.first_person = v.render.polymod == MOOG_POLYMOD_FIRST_PERSON ? 1 : 0;
+      if (ms.first_person) { ms.fp_slot0 = prog->layer_slot0[v.render.polymod_layer]; ms.fp_nslots = prog->layer_nslots[v.render.polymod_layer]; }
+      ms.bg = ((uint32_t)v.render.bg[0] & 255u) | (((uint32_t)v.render.bg[1] & 255u) << 8) | (((uint32_t)v.render.bg[2] & 255u) << 16);
+      // row records per pass: 192 (the headline workload's frames have ~170 rows behind the cached walls), at least a
+      // canvas height so that any one polygon fits; frames with more rows take several passes
+      // (frames that want more keep the records growing: mask_rows_grow, before a launch)
+      int cap = 192;
+      { const char* rc = getenv("MOOG_RASTER_ROWS"); if (rc && atoi(rc) >= 1) { cap = atoi(rc); v.raster_rows_fixed = 1; } }   // tuning / tests of the multi-pass path
+      mask_plan_rows(e, v, cap);
+      {   // 4-byte edge records when the 16-byte ones keep frames off a CU (or do not fit at all): MOOG_RASTER_COMPACT=0 / 1 forces
+        const char* cs = getenv("MOOG_RASTER_COMPACT");
+        const RmSetup full = ms;
+        ms.compact = 1; ms.ok = 1;
+        mask_plan_rows(e, v, cap);
+        // (the 4-byte records cost the rows phase a tenth more instructions -- headline workload 49.5 -> 53 us when they were picked for
+        //  it by mistake -- so they are for programs whose 16-byte records leave a CU clearly short of the frames its registers allow)
+        const int by_regs = RM_WAVES_PER_SIMD * 4 / (RM_THREADS / 64);
+        const bool better = ms.ok && (!full.ok || ((int)(160u * 1024u / full.lds) < by_regs - 1 && mask_frames_per_cu(ms.lds) > mask_frames_per_cu(full.lds)));
+        if (cs ? atoi(cs) == 0 : !better) ms = full;
+      }
+      v.mask_free_cap = (ms.ok && !v.raster_rows_fixed) ? mask_free_rows(e, v) : ms.cap_rows;
+      if (ms.ok) {   // a draw record per env (moog_draw_record.h): header + an item per slot and copy + every vertex slot's point and owner byte
+        v.draw_lay = rm_draw_layout(ms.S, e->L.TOTV * ms.ncopy);
+        if (hipMalloc(&v.draw, (size_t)e->n_envs * v.draw_lay.stride) != hipSuccess) {
+          return fail(MOOG_E_NOMEM, "out of device memory (draw records)");
+        }
+      }
+    }
+  }
+  // (coherent = fine-grained: the kernels' system-scope atomics and the host's atomic read / clear meet in the same memory)
+  if (hipHostMalloc(reinterpret_cast<void**>(&v.rows_seen), 2 * sizeof(int32_t), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) { v.rows_seen[0] = 0; v.rows_seen[1] = 0; }   // ([1]: how many frames wanted more: for tools)
+  else v.rows_seen = nullptr;   // (without it the records keep their first size)
+  return MOOG_OK;
+}
+
 int moog_engine_create(const moog_program_t* prog, int32_t n_envs, int32_t device_id, uint64_t seed,
                        int64_t env_index0, moog_engine_t** out) {
   if (!out) return fail(MOOG_E_INVALID, "null out");
@@ -555,6 +725,7 @@ int moog_engine_create(const moog_program_t* prog, int32_t n_envs, int32_t devic
   HIPCHK(hipSetDevice(device_id));
   moog_engine* e = new moog_engine();
   e->prog = *prog;
+  e->frameless = prog->render.width == 0 && prog->render.height == 0;
   moog_layout(prog, &e->L);
   e->n_envs = n_envs;
   e->device = device_id;
@@ -606,114 +777,11 @@ int moog_engine_create(const moog_program_t* prog, int32_t n_envs, int32_t devic
     free_engine(e);
     return fail(MOOG_E_UNSUPPORTED, "state record does not fit in 160 KB of LDS");
   }
-  // raster LDS plan (moog_raster.h): row records for `chunk` rows per pass
-  {
-    // Tiles: the row masks of the kernel are 128 bits, so a wider canvas is cut into columns of the widest
-    // multiple of 16 <= 128 that divides the width, and a taller one into bands of 64 rows.
-    e->aa = prog->render.aa > 1 ? prog->render.aa : 1;
-    e->canvas_w = e->aa * prog->render.width;
-    e->canvas_h = e->aa * prog->render.height;
-    e->pad_w = (e->canvas_w + 15) & ~15;
-    int tw = e->pad_w <= 128 ? e->pad_w : 128;
-    while (e->pad_w % tw != 0) tw -= 16;
-    e->raster_tile_w = tw;
-    e->raster_tiles_x = e->pad_w / tw;
-    e->raster_band_h = e->canvas_h <= 128 ? e->canvas_h : 64;
-    {   // frames that will use the per-env prefix (setup_env_prefix): few sprites are left to draw per tile and the per-tile fixed
-        // cost dominates -- whole-height tiles measured 1.65 against 1.73 ms per 4096 pacman frames (profiles/r04_env_prefix.txt)
-        // (decided here, from what the PROGRAM allows: the tile plan sizes every LDS table.  A handle that later runs without the prefix --
-        //  allocation failure, a prefix that shrank to nothing, a colour override -- keeps the whole-height tiles: 1.65 ms against 1.73 ms
-        //  with 64-row bands WITH the prefix, 2.45 against 2.51 ms WITHOUT it in the same file: not a loss either way)
-      int nsv_ = 0;
-      const char* sw = getenv("MOOG_RASTER_ENV_BG");
-      if (e->canvas_h > 128 && e->canvas_h <= 256 && e->aa <= 1 && !(sw && atoi(sw) == 0) && env_prefix_slots(prog, &nsv_) >= 32)
-        e->raster_band_h = e->canvas_h;
-    }
-    e->raster_bands = (e->canvas_h + e->raster_band_h - 1) / e->raster_band_h;
-    int W = e->raster_tile_w, H = e->raster_band_h;   // (the LDS plan is per tile)
-    int ncopy = prog->render.polymod == MOOG_POLYMOD_TORUS ? 9 : 1;
-    int items = prog->n_slots * ncopy;
-    if (items < 1) items = 1;
-    e->raster_words = (W + 63) / 64;
-    e->raster_iwords = (items + 31) / 32;
-    int maxv = 2;
-    for (int sl = 0; sl < prog->n_slots; ++sl) if (prog->slot_vcap[sl] > maxv) maxv = prog->slot_vcap[sl];
-    e->raster_xxcap = 2 * maxv;
-    e->raster_hwords = (maxv + 31) / 32;
-    RPlan pl;
-    // Row records per pass: 376 (>= H so that any item fits; sized so that six workgroups of the
-    // 4096 x 32-sprite workload share a CU), then as many more as fit without costing a resident
-    // workgroup (frames with more rows than records take several passes).
-    int cap = items * H;
-    if (cap > 376) cap = 376;
-    if (cap < H) cap = H;
-    raster_plan(prog->n_slots, e->L.TOTV, ncopy, W, H, cap, e->raster_iwords, e->raster_hwords, e->raster_xxcap, &pl);
-    {
-      const unsigned lds_cu = 160 * 1024;
-      unsigned wgs = pl.total ? lds_cu / pl.total : 0;
-      if (wgs > 6) wgs = 6;   // registers hold six workgroups per CU at most
-      const int want = items * H < 4096 ? items * H : 4096;
-      while (wgs && cap < want) {
-        RPlan p2;
-        int c2 = cap + 32 < want ? cap + 32 : want;
-        raster_plan(prog->n_slots, e->L.TOTV, ncopy, W, H, c2, e->raster_iwords, e->raster_hwords, e->raster_xxcap, &p2);
-        if (lds_cu / p2.total < wgs) break;
-        cap = c2; pl = p2;
-      }
-    }
-    { const char* rc = getenv("MOOG_RASTER_ROWS"); if (rc && atoi(rc) >= H) cap = atoi(rc); }   // tuning / tests of the multi-pass path
-    raster_plan(prog->n_slots, e->L.TOTV, ncopy, W, H, cap, e->raster_iwords, e->raster_hwords, e->raster_xxcap, &pl);
-    if (pl.total > 160 * 1024 || (size_t)e->L.TOTV * ncopy >= (1u << 20)) {
-      free_engine(e);
-      return fail(MOOG_E_UNSUPPORTED, "raster working set does not fit in LDS");
-    }
-    e->raster_chunk = cap;
-    e->raster_plan_ = pl;
-    e->raster_lds = pl.total;
-  }
-  {   // mask rasteriser (moog_raster_mask_core.h): one-tile frames, polygons of <= 128 vertices, at most 256 polygons (a torus has nine per sprite)
-    RmSetup& ms = e->mask_setup;
-    memset(&ms, 0, sizeof ms);
-    int maxv = 1;
-    for (int sl = 0; sl < prog->n_slots; ++sl) if (prog->slot_vcap[sl] > maxv) maxv = prog->slot_vcap[sl];
-    const int ncopy = prog->render.polymod == MOOG_POLYMOD_TORUS ? 9 : 1;
-    const char* sw = getenv("MOOG_RASTER_MASK");   // 0: the push / sort / span kernel for every frame (A/B runs, tests)
-    ms.ok = !(sw && atoi(sw) == 0) && e->raster_tiles_x * e->raster_bands == 1 && e->pad_w <= 128 && e->canvas_h <= 128 &&
-            maxv <= RM_BIG_NV && prog->n_slots >= 1 && prog->n_slots * ncopy <= 256 && e->L.TOTV >= 1;
-    if (ms.ok) {
-      ms.slots = prog->n_slots; ms.ncopy = ncopy; ms.big = maxv > RM_MAX_NV ? 1 : 0;
-      ms.S = prog->n_slots * ncopy;
-      ms.iwords = (ms.S + 31) / 32;
-      ms.cmap = prog->render.cmap;
-      ms.first_person = prog->render.polymod == MOOG_POLYMOD_FIRST_PERSON ? 1 : 0;
-      if (ms.first_person) { ms.fp_slot0 = prog->layer_slot0[prog->render.polymod_layer]; ms.fp_nslots = prog->layer_nslots[prog->render.polymod_layer]; }
-      ms.bg = ((uint32_t)prog->render.bg[0] & 255u) | (((uint32_t)prog->render.bg[1] & 255u) << 8) | (((uint32_t)prog->render.bg[2] & 255u) << 16);
-      // row records per pass: 192 (the headline workload's frames have ~170 rows behind the cached walls), at least a
-      // canvas height so that any one polygon fits; frames with more rows take several passes
-      // (frames that want more keep the records growing: mask_rows_grow, before a launch)
-      int cap = 192;
-      { const char* rc = getenv("MOOG_RASTER_ROWS"); if (rc && atoi(rc) >= 1) { cap = atoi(rc); e->raster_rows_fixed = 1; } }   // tuning / tests of the multi-pass path
-      mask_plan_rows(e, cap);
-      {   // 4-byte edge records when the 16-byte ones keep frames off a CU (or do not fit at all): MOOG_RASTER_COMPACT=0 / 1 forces
-        const char* cs = getenv("MOOG_RASTER_COMPACT");
-        const RmSetup full = ms;
-        ms.compact = 1; ms.ok = 1;
-        mask_plan_rows(e, cap);
-        // (the 4-byte records cost the rows phase a tenth more instructions -- headline workload 49.5 -> 53 us when they were picked for
-        //  it by mistake -- so they are for programs whose 16-byte records leave a CU clearly short of the frames its registers allow)
-        const int by_regs = RM_WAVES_PER_SIMD * 4 / (RM_THREADS / 64);
-        const bool better = ms.ok && (!full.ok || ((int)(160u * 1024u / full.lds) < by_regs - 1 && mask_frames_per_cu(ms.lds) > mask_frames_per_cu(full.lds)));
-        if (cs ? atoi(cs) == 0 : !better) ms = full;
-      }
-      e->mask_free_cap = (ms.ok && !e->raster_rows_fixed) ? mask_free_rows(e) : ms.cap_rows;
-      if (ms.ok) {   // a draw record per env (moog_draw_record.h): header + an item per slot and copy + every vertex slot's point and owner byte
-        e->draw_lay = rm_draw_layout(ms.S, e->L.TOTV * ms.ncopy);
-        if (hipMalloc(&e->draw, (size_t)e->n_envs * e->draw_lay.stride) != hipSuccess) {
-          free_engine(e);
-          return fail(MOOG_E_NOMEM, "out of device memory (draw records)");
-        }
-      }
-    }
+  if (!e->frameless) {
+    e->views[0].render = prog->render;
+    e->views[0].P = e->d_prog;
+    const int rc = setup_view(e, e->views[0], true);
+    if (rc) { free_engine(e); return rc; }
   }
   {
     int (*const configure[6])(size_t) = {moog_configure_step_f3, moog_configure_step_f4, moog_configure_step_t3,
@@ -734,18 +802,15 @@ int moog_engine_create(const moog_program_t* prog, int32_t n_envs, int32_t devic
   if (err == hipSuccess)
     err = (hipError_t)moog_configure_reset_plain(e->step_lds);
     if (err == hipSuccess) err = (hipError_t)moog_configure_reset_full(e->step_lds);
-  if (err == hipSuccess)
-    err = (hipError_t)moog_raster_configure(e->raster_lds);
-  if (err == hipSuccess && e->mask_setup.ok) err = (hipError_t)moog_raster_configure_mask(64 * 1024);   // (the records may grow: mask_rows_grow)
+  if (err == hipSuccess && !e->frameless)
+    err = (hipError_t)moog_raster_configure(e->views[0].raster_lds);
+  if (err == hipSuccess && e->views[0].mask_setup.ok) err = (hipError_t)moog_raster_configure_mask(64 * 1024);   // (the records may grow: mask_rows_grow)
   if (err != hipSuccess) {
     free_engine(e);
     return fail(MOOG_E_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(err));
   }
   { const char* ds = getenv("MOOG_STEP_DEBUG"); e->step_dbg = ds ? atoi(ds) : 0; }
   { const char* ds = getenv("MOOG_RASTER_STOP"); e->raster_stop = ds ? atoi(ds) : 0; }
-  // (coherent = fine-grained: the kernels' system-scope atomics and the host's atomic read / clear meet in the same memory)
-  if (hipHostMalloc(reinterpret_cast<void**>(&e->rows_seen), 2 * sizeof(int32_t), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) { e->rows_seen[0] = 0; e->rows_seen[1] = 0; }   // ([1]: how many frames wanted more: for tools)
-  else e->rows_seen = nullptr;   // (without it the records keep their first size)
   if (hipHostMalloc(reinterpret_cast<void**>(&e->fault_flag), sizeof(int32_t), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
     free_engine(e);
     return fail(MOOG_E_NOMEM, "hipHostMalloc(fault flag) failed");
@@ -759,12 +824,16 @@ int moog_engine_create(const moog_program_t* prog, int32_t n_envs, int32_t devic
         return fail(MOOG_E_NOMEM, "hipMalloc(layer usage) failed");
       }
     }
-  int rc2 = build_static_prefix(e);
-  if (rc2 == MOOG_OK) rc2 = setup_anti_aliasing(e);
-  if (rc2 == MOOG_OK) rc2 = setup_env_prefix(e);
-  if (rc2 == MOOG_OK && e->aa <= 1 && e->pad_w != e->canvas_w &&
-      hipMalloc(&e->pad_img, (size_t)n_envs * e->canvas_h * e->pad_w * 3) != hipSuccess)
-    rc2 = fail(MOOG_E_NOMEM, "hipMalloc(16-aligned frames) failed");
+  int rc2 = MOOG_OK;
+  if (!e->frameless) {
+    RView& v = e->views[0];
+    rc2 = build_static_prefix(e, v);
+    if (rc2 == MOOG_OK) rc2 = setup_anti_aliasing(e, v);
+    if (rc2 == MOOG_OK) rc2 = setup_env_prefix(e);
+    if (rc2 == MOOG_OK && v.aa <= 1 && v.pad_w != v.canvas_w &&
+        hipMalloc(&v.pad_img, (size_t)n_envs * v.canvas_h * v.pad_w * 3) != hipSuccess)
+      rc2 = fail(MOOG_E_NOMEM, "hipMalloc(16-aligned frames) failed");
+  }
   if (rc2) { free_engine(e); return rc2; }
   *out = e;
   return MOOG_OK;
@@ -881,15 +950,15 @@ static void launch_step(moog_engine* e, hipStream_t s, const KArgs& a) {
 
 // What the draw-record emitter needs (moog_draw_record.h): by value in the step kernel's and the derive kernel's arguments.
 // out = null when this engine's frames are not the mask rasteriser's.
-static RmEmit emit_args(moog_engine* e) {
+static RmEmit emit_args(moog_engine* e, const RView& v) {
   RmEmit m;
   memset(&m, 0, sizeof m);
-  const RmSetup& ms = e->mask_setup;
-  if (!ms.ok || !e->draw) return m;
-  m.out = e->draw; m.lay = e->draw_lay;
-  m.S = ms.S; m.slots = ms.slots; m.ncopy = ms.ncopy; m.W = e->pad_w; m.H = e->canvas_h; m.scale_w = e->canvas_w;
+  const RmSetup& ms = v.mask_setup;
+  if (!ms.ok || !v.draw) return m;
+  m.out = v.draw; m.lay = v.draw_lay;
+  m.S = ms.S; m.slots = ms.slots; m.ncopy = ms.ncopy; m.W = v.pad_w; m.H = v.canvas_h; m.scale_w = v.canvas_w;
   m.cmap = ms.cmap; m.first_person = ms.first_person; m.fp_slot0 = ms.fp_slot0; m.fp_nslots = ms.fp_nslots;
-  m.n_static = (e->s_f64 && ms.ncopy == 1) ? e->n_static : 0;
+  m.n_static = (e->s_f64 && ms.ncopy == 1) ? v.n_static : 0;
   m.sref_v = e->s_f64 ? e->s_f64 + e->L.o_verts : nullptr;
   m.sref_col = e->s_f64 ? e->s_f64 + e->L.o_color : nullptr;
   m.sref_flags = e->s_i32 ? e->s_i32 + e->L.o_flags : nullptr;
@@ -902,34 +971,35 @@ static RmEmit emit_args(moog_engine* e) {
 // when those frames are the mask rasteriser's, drawn in one launch over every env (a late-reset program's episodes are opened by
 // the reset kernel behind the step kernel: that launch writes the draw records of the envs it resets).
 static bool step_emits_draw(moog_engine* e) {
+  const RView& v = e->views[0];
   // (the emitter's scratch in the step kernel's LDS, emit_draw_record: a torus's nine items per slot must fit behind the vertex offsets)
-  const bool scratch_fits = e->mask_setup.ncopy == 1 ||
-      4u * (size_t)RM_EMIT_SCRATCH_WORDS(e->mask_setup.slots, e->mask_setup.S, e->mask_setup.ncopy) <= (size_t)CAND_CAP * 2 + 128 + 64 * 8;
-  return e->mask_setup.ok && e->draw && e->pe_ns <= 0 && e->aa <= 1 && scratch_fits;
+  const bool scratch_fits = v.mask_setup.ncopy == 1 ||
+      4u * (size_t)RM_EMIT_SCRATCH_WORDS(v.mask_setup.slots, v.mask_setup.S, v.mask_setup.ncopy) <= (size_t)CAND_CAP * 2 + 128 + 64 * 8;
+  return v.mask_setup.ok && v.draw && e->pe_ns <= 0 && v.aa <= 1 && scratch_fits;
 }
 
-static RArgs raster_args(moog_engine* e, uint8_t* image) {
+static RArgs raster_args(moog_engine* e, RView& v, uint8_t* image) {
   RArgs r;
-  if (e->mask_setup.ok) mask_rows_grow(e);
-  r.ms = e->mask_setup;
+  if (v.mask_setup.ok) mask_rows_grow(e, v);
+  r.ms = v.mask_setup;
   // (frames report only while the records can still grow: every report is an atomic on host memory)
-  r.rows_seen = (e->raster_rows_fixed || e->mask_setup.cap_rows >= e->mask_free_cap) ? nullptr : e->rows_seen;
-  r.P = e->d_prog; r.L = e->L; r.f64 = e->view.f64; r.i32 = e->view.i32; r.image = image;
-  r.vinfo = e->d_vinfo; r.plan = e->raster_plan_;
-  r.n_envs = e->n_envs; r.chunk = e->raster_chunk; r.words = e->raster_words;
-  r.tile_w = e->raster_tile_w; r.band_h = e->raster_band_h; r.tiles_x = e->raster_tiles_x; r.bands = e->raster_bands;
-  r.canvas_w = e->pad_w; r.scale_w = e->canvas_w; r.canvas_h = e->canvas_h; r.flip = e->aa > 1 ? 0 : 1;
-  r.iwords = e->raster_iwords; r.hwords = e->raster_hwords; r.xxcap = e->raster_xxcap;
+  r.rows_seen = (v.raster_rows_fixed || v.mask_setup.cap_rows >= v.mask_free_cap) ? nullptr : v.rows_seen;
+  r.P = v.P; r.L = e->L; r.f64 = e->view.f64; r.i32 = e->view.i32; r.image = image;
+  r.vinfo = e->d_vinfo; r.plan = v.raster_plan_;
+  r.n_envs = e->n_envs; r.chunk = v.raster_chunk; r.words = v.raster_words;
+  r.tile_w = v.raster_tile_w; r.band_h = v.raster_band_h; r.tiles_x = v.raster_tiles_x; r.bands = v.raster_bands;
+  r.canvas_w = v.pad_w; r.scale_w = v.canvas_w; r.canvas_h = v.canvas_h; r.flip = v.aa > 1 ? 0 : 1;
+  r.iwords = v.raster_iwords; r.hwords = v.raster_hwords; r.xxcap = v.raster_xxcap;
   r.debug_stop = e->raster_stop;
-  r.n_static = e->n_static; r.nsv = e->nsv; r.build = 0;
+  r.n_static = v.n_static; r.nsv = v.nsv; r.build = 0;
   r.sref_v = e->s_f64 ? e->s_f64 + e->L.o_verts : nullptr;
   r.sref_col = e->s_f64 ? e->s_f64 + e->L.o_color : nullptr;
   r.sref_flags = e->s_i32 ? e->s_i32 + e->L.o_flags : nullptr;
   r.sref_nv = e->s_i32 ? e->s_i32 + e->L.o_nverts : nullptr;
   r.sref_opa = e->s_i32 ? e->s_i32 + e->L.o_opacity : nullptr;
-  r.sbg = e->s_bg;
+  r.sbg = v.s_bg;
   r.sbg_env_stride = 0; r.env_build = nullptr; r.rgb_override = e->rgb_override;
-  r.em = emit_args(e); r.draw_ready = 0; r.env0 = 0;
+  r.em = emit_args(e, v); r.draw_ready = 0; r.env0 = 0;
   return r;
 }
 
@@ -953,39 +1023,80 @@ static int use_env_prefix(moog_engine* e, RArgs& r, hipStream_t s) {
   RArgs b = r;
   b.image = e->pe_bg; b.n_static = e->pe_ns; b.nsv = e->pe_nsv; b.build = 1; b.env_build = e->pe_build; b.debug_stop = 0;
   b.sbg = nullptr; b.sbg_env_stride = 0;
-  moog_raster_launch(b, e->raster_lds, s);
+  moog_raster_launch(b, e->views[0].raster_lds, s);
   r.n_static = e->pe_ns; r.nsv = e->pe_nsv; r.sbg = e->pe_bg;
-  r.sbg_env_stride = (size_t)e->canvas_h * e->pad_w * 3;
+  r.sbg_env_stride = (size_t)e->views[0].canvas_h * e->views[0].pad_w * 3;
   return MOOG_OK;
 }
 
-static int launch_raster(moog_engine* e, uint8_t* image, hipStream_t s, int timed = -1, bool draw_ready = false) {
-  RArgs r = raster_args(e, image);
+// One view's frames: its raster launch (mask or span kernel; the mask kernel derives the draw records first unless draw_ready),
+// plus the crop of a 16-aligned canvas or the LANCZOS resize of an anti-aliased one.  Not bracketed: launch_frames times.
+static int launch_raster(moog_engine* e, RView& v, uint8_t* image, hipStream_t s, bool draw_ready = false) {
+  RArgs r = raster_args(e, v, image);
   r.draw_ready = draw_ready ? 1 : 0;
-  Bracket br(e, MOOG_K_RASTER, s, timed);
-  if (e->aa <= 1) { const int rc = use_env_prefix(e, r, s); if (rc) return rc; }
-  if (e->aa <= 1 && e->pad_w != e->canvas_w) {   // drawn 16-aligned, cropped into the caller's frames
-    r.image = e->pad_img;
-    moog_raster_launch(r, e->raster_lds, s);
-    moog_crop_launch(e->pad_img, image, (size_t)e->n_envs * e->canvas_h, e->pad_w * 3, e->canvas_w * 3, s);
-  } else if (e->aa <= 1) {
-    moog_raster_launch(r, e->raster_lds, s);
+  if (v.aa <= 1 && &v == &e->views[0]) { const int rc = use_env_prefix(e, r, s); if (rc) return rc; }
+  if (v.aa <= 1 && v.pad_w != v.canvas_w) {   // drawn 16-aligned, cropped into the caller's frames
+    r.image = v.pad_img;
+    moog_raster_launch(r, v.raster_lds, s);
+    moog_crop_launch(v.pad_img, image, (size_t)e->n_envs * v.canvas_h, v.pad_w * 3, v.canvas_w * 3, s);
+  } else if (v.aa <= 1) {
+    moog_raster_launch(r, v.raster_lds, s);
   } else {   // pil_renderer.py:111-112: draw on the large canvas, then Image.resize(LANCZOS); a chunk of envs at a time
-    const size_t frame = (size_t)e->prog.render.width * e->prog.render.height * 3;
-    for (int e0 = 0; e0 < e->n_envs; e0 += e->aa_chunk) {
-      const int n = e->n_envs - e0 < e->aa_chunk ? e->n_envs - e0 : e->aa_chunk;
+    const size_t frame = (size_t)v.render.width * v.render.height * 3;
+    for (int e0 = 0; e0 < e->n_envs; e0 += v.aa_chunk) {
+      const int n = e->n_envs - e0 < v.aa_chunk ? e->n_envs - e0 : v.aa_chunk;
       RArgs c = r;
       c.f64 = r.f64 + (size_t)e0 * e->L.f64_per_env;
       c.i32 = r.i32 + (size_t)e0 * e->L.i32_per_env;
       c.image = e->aa_canvas;
       c.n_envs = n;
-      c.env0 = e0; c.draw_ready = 0;
-      moog_raster_launch(c, e->raster_lds, s);
-      moog_resize_launch(e->aa_resize, e->aa_canvas, e->aa_tmp, image + (size_t)e0 * frame, n, s);
+      c.env0 = e0; c.draw_ready = (e0 == 0 && n == e->n_envs) ? r.draw_ready : 0;   // (records derived ahead cover one chunk of every env)
+      moog_raster_launch(c, v.raster_lds, s);
+      moog_resize_launch(v.aa_resize, e->aa_canvas, e->aa_tmp, image + (size_t)e0 * frame, n, s);
     }
   }
   HIPCHK(hipGetLastError());
   return MOOG_OK;
+}
+
+// Whether the draw records of view v can be derived ahead of its raster launch, in the one derive launch of the extra views:
+// mask-path frames drawn in one launch over every env (not on top of the per-env prefix: those are the span kernel's).
+static bool derives_ahead(moog_engine* e, const RView& v) {
+  if (!v.mask_setup.ok || !v.draw) return false;
+  if (&v == &e->views[0] && e->pe_ns > 0) return false;
+  return v.aa <= 1 || v.aa_chunk >= e->n_envs;
+}
+
+// Every view's frames of one call: the primary's into `image` (timed as MOOG_K_RASTER, exactly as an engine without extra
+// views draws them), then -- under MOOG_K_VIEWS -- one derive launch for the draw records of every extra view on the mask path
+// (and of the primary, when its records were not written by the step kernel), the extra views' raster launches, and the
+// primary's raster launch behind them.
+static int launch_frames(moog_engine* e, uint8_t* image, hipStream_t s, bool draw_ready = false, int timed = -1) {
+  RView* extra[MOOG_MAX_VIEWS];
+  int n_extra = 0;
+  for (int k = 1; k < e->n_views; ++k) if (e->views[k].image) extra[n_extra++] = &e->views[k];
+  if (n_extra == 0) {
+    Bracket br(e, MOOG_K_RASTER, s, timed);
+    return launch_raster(e, e->views[0], image, s, draw_ready);
+  }
+  RView& p = e->views[0];
+  const bool join = !draw_ready && derives_ahead(e, p);   // the primary's records join the extra views' derive launch
+  {
+    Bracket br(e, MOOG_K_VIEWS, s);
+    RmEmit em[MOOG_MAX_VIEWS];
+    bool ahead[MOOG_MAX_VIEWS] = {};
+    int n_em = 0;
+    if (join) em[n_em++] = emit_args(e, p);
+    for (int k = 0; k < n_extra; ++k)
+      if (derives_ahead(e, *extra[k])) { ahead[k] = true; em[n_em++] = emit_args(e, *extra[k]); }
+    if (n_em > 0) moog_derive_launch(em, n_em, raster_args(e, p, image), s);
+    for (int k = 0; k < n_extra; ++k) {
+      const int rc = launch_raster(e, *extra[k], extra[k]->image, s, ahead[k]);
+      if (rc) return rc;
+    }
+  }
+  Bracket br(e, MOOG_K_RASTER, s, timed);
+  return launch_raster(e, p, image, s, draw_ready || join);
 }
 
 // Reset pool: one fill launch behind the call that has just been enqueued on `s`, on the side streams in turn.  A fill
@@ -1041,6 +1152,7 @@ int moog_engine_reset(moog_engine_t* e, const uint8_t* env_mask_dev, const moog_
                       const moog_step_out_t* out, void* hip_stream) {
   int rc = ready(e);
   if (rc) return rc;
+  if (out && out->image && e->frameless) return fail(MOOG_E_INVALID, FRAMELESS_MSG);
   hipStream_t s = (hipStream_t)hip_stream;
   KArgs a = make_args(e, nullptr, inject, out, MODE_RESET_MASK, env_mask_dev);
   if (e->pool_on && (rc = pool_drop(e, s)) != MOOG_OK) return rc;
@@ -1050,7 +1162,7 @@ int moog_engine_reset(moog_engine_t* e, const uint8_t* env_mask_dev, const moog_
   }
   HIPCHK(hipGetLastError());
   if (e->pool_on && !(inject && inject->uniforms) && (rc = pool_kick(e, s)) != MOOG_OK) return rc;
-  if (out && out->image) return launch_raster(e, out->image, s);
+  if (out && out->image) return launch_frames(e, out->image, s);
   return MOOG_OK;
 }
 
@@ -1059,11 +1171,12 @@ int moog_engine_step(moog_engine_t* e, const void* actions_dev, const moog_injec
   int rc = ready(e);
   if (rc) return rc;
   if (!actions_dev) return fail(MOOG_E_INVALID, "null actions");
+  if (out && out->image && e->frameless) return fail(MOOG_E_INVALID, FRAMELESS_MSG);
   hipStream_t s = (hipStream_t)hip_stream;
   // (envs whose episode ended in the previous call are reset inside the step kernel, environment.py:100-101)
   KArgs a = make_args(e, actions_dev, inject, out, MODE_STEP, nullptr);
   const bool emit = out && out->image && step_emits_draw(e);
-  if (emit) a.draw = emit_args(e);
+  if (emit) a.draw = emit_args(e, e->views[0]);
   if (e->sched_pending) {   // the order computed from the previous step's costs
     HIPCHK(hipStreamWaitEvent(s, e->ev_sched_done, 0));
     e->sched_pending = false;
@@ -1083,7 +1196,7 @@ int moog_engine_step(moog_engine_t* e, const void* actions_dev, const moog_injec
     HIPCHK(hipEventRecord(e->ev_sched_done, e->sched_stream));
     e->sched_pending = true;
   }
-  if (out && out->image) return launch_raster(e, out->image, s, -1, emit);
+  if (out && out->image) return launch_frames(e, out->image, s, emit);
   return MOOG_OK;
 }
 
@@ -1104,7 +1217,8 @@ int moog_engine_render(moog_engine_t* e, uint8_t* image_dev, void* hip_stream) {
   int rc = ready(e);
   if (rc) return rc;
   if (!image_dev) return fail(MOOG_E_INVALID, "null image");
-  return launch_raster(e, image_dev, (hipStream_t)hip_stream);
+  if (e->frameless) return fail(MOOG_E_INVALID, FRAMELESS_MSG);
+  return launch_frames(e, image_dev, (hipStream_t)hip_stream);
 }
 
 int moog_engine_set_schedule(moog_engine_t* e, int32_t* perm_dev, float* cost_dev) {
@@ -1224,21 +1338,80 @@ int moog_engine_step_kernel(moog_engine_t* e, int32_t* specialised) {
 
 int moog_engine_read_draw_records(moog_engine_t* e, uint8_t* host_out, int64_t bytes, int64_t* stride, int32_t* in_step) {
   if (!e) return fail(MOOG_E_INVALID, "null engine");
-  if (!e->mask_setup.ok || !e->draw) return fail(MOOG_E_UNSUPPORTED, "this program's frames are not the mask rasteriser's: no draw records");
-  if (stride) *stride = (int64_t)e->draw_lay.stride;
+  const RView& v = e->views[0];
+  if (!v.mask_setup.ok || !v.draw) return fail(MOOG_E_UNSUPPORTED, "this program's frames are not the mask rasteriser's: no draw records");
+  if (stride) *stride = (int64_t)v.draw_lay.stride;
   if (in_step) *in_step = step_emits_draw(e) ? 1 : 0;
   if (!host_out) return MOOG_OK;
-  const int64_t need = (int64_t)e->n_envs * (int64_t)e->draw_lay.stride;
+  const int64_t need = (int64_t)e->n_envs * (int64_t)v.draw_lay.stride;
   if (bytes < need) return fail(MOOG_E_INVALID, "host buffer too small for the draw records");
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(host_out, e->draw, (size_t)need, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(host_out, v.draw, (size_t)need, hipMemcpyDeviceToHost));
   return MOOG_OK;
 }
 
-int moog_engine_raster_path(moog_engine_t* e, int32_t* path) {
+int moog_engine_raster_path(moog_engine_t* e, int32_t* path) { return moog_engine_view_raster_path(e, 0, path); }
+
+int moog_engine_view_raster_path(moog_engine_t* e, int32_t view, int32_t* path) {
   if (!e || !path) return fail(MOOG_E_INVALID, "null argument");
-  *path = (e->mask_setup.ok && e->pe_ns <= 0) ? (e->mask_setup.compact ? MOOG_RASTER_MASK_COMPACT : MOOG_RASTER_MASK) : MOOG_RASTER_SPANS;
+  if (e->frameless) return fail(MOOG_E_INVALID, FRAMELESS_MSG);
+  if (view < 0 || view >= e->n_views) return fail(MOOG_E_INVALID, "no such view");
+  const RmSetup& ms = e->views[view].mask_setup;
+  const bool prefix = view == 0 && e->pe_ns > 0;   // (frames on top of the per-env prefix are the span kernel's)
+  *path = (ms.ok && !prefix) ? (ms.compact ? MOOG_RASTER_MASK_COMPACT : MOOG_RASTER_MASK) : MOOG_RASTER_SPANS;
+  return MOOG_OK;
+}
+
+int moog_engine_add_view(moog_engine_t* e, const moog_render_t* render, int32_t* view) {
+  if (!e || !render || !view) return fail(MOOG_E_INVALID, "null argument");
+  if (e->frameless) return fail(MOOG_E_INVALID, "this program draws no frames (render 0 x 0): it takes no extra views");
+  if (e->n_views >= MOOG_MAX_VIEWS) return fail(MOOG_E_UNSUPPORTED, "at most MOOG_MAX_VIEWS views per engine");
+  int rc = validate_render(&e->prog, render);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(e->device));
+  RView& v = e->views[e->n_views];
+  v = RView();
+  v.render = *render;
+  moog_program_t* host = new moog_program_t(e->prog);   // (the span kernel reads P->render: a device program of the view's own)
+  host->render = *render;
+  hipError_t err = hipMalloc(&v.d_own, sizeof(moog_program_t));
+  if (err == hipSuccess) err = hipMemcpy(v.d_own, host, sizeof(moog_program_t), hipMemcpyHostToDevice);
+  delete host;
+  v.P = v.d_own;
+  if (err == hipSuccess) rc = setup_view(e, v, false);
+  else rc = fail(MOOG_E_NOMEM, "hipMalloc(view program) failed");
+  if (rc == MOOG_OK) rc = build_static_prefix(e, v);
+  if (rc == MOOG_OK) rc = setup_anti_aliasing(e, v);
+  if (rc == MOOG_OK && v.aa <= 1 && v.pad_w != v.canvas_w &&
+      hipMalloc(&v.pad_img, (size_t)e->n_envs * v.canvas_h * v.pad_w * 3) != hipSuccess)
+    rc = fail(MOOG_E_NOMEM, "hipMalloc(16-aligned frames) failed");
+  if (rc == MOOG_OK) {   // (the kernels' LDS limit is process-wide and only grows: moog_raster_configure)
+    err = (hipError_t)moog_raster_configure(v.raster_lds);
+    if (err == hipSuccess && v.mask_setup.ok) err = (hipError_t)moog_raster_configure_mask(64 * 1024);
+    if (err != hipSuccess) rc = fail(MOOG_E_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(err));
+  }
+  if (rc == MOOG_OK && e->rgb_override) { v.kept_n_static = v.n_static; v.n_static = 0; }
+  if (rc) {
+    const std::string msg = g_err;
+    if (v.d_own) hipFree(v.d_own);
+    if (v.draw) hipFree(v.draw);
+    if (v.s_bg) hipFree(v.s_bg);
+    if (v.pad_img) hipFree(v.pad_img);
+    if (v.aa_tables) hipFree(v.aa_tables);
+    if (v.rows_seen) hipHostFree(v.rows_seen);
+    v = RView();
+    g_err = msg;
+    return rc;
+  }
+  *view = e->n_views++;
+  return MOOG_OK;
+}
+
+int moog_engine_set_view_image(moog_engine_t* e, int32_t view, uint8_t* image_dev) {
+  if (!e) return fail(MOOG_E_INVALID, "null engine");
+  if (view < 1 || view >= e->n_views) return fail(MOOG_E_INVALID, "no such extra view (the primary's frames are the calls' own image)");
+  e->views[view].image = image_dev;
   return MOOG_OK;
 }
 
@@ -1253,10 +1426,12 @@ int moog_engine_kernel_variant(moog_engine_t* e, int32_t* variant, int32_t* late
 int moog_engine_set_color_override(moog_engine_t* e, const uint32_t* rgb_dev) {
   if (!e) return fail(MOOG_E_INVALID, "null engine");
   if (rgb_dev && !e->rgb_override) {   // the cached pictures hold the colour map's colours: off while the host supplies them
-    e->kept_n_static = e->n_static; e->kept_pe_ns = e->pe_ns; e->kept_pe_nsv = e->pe_nsv;
-    e->n_static = 0; e->pe_ns = 0; e->pe_nsv = 0;
+    for (int k = 0; k < e->n_views; ++k) { e->views[k].kept_n_static = e->views[k].n_static; e->views[k].n_static = 0; }
+    e->kept_pe_ns = e->pe_ns; e->kept_pe_nsv = e->pe_nsv;
+    e->pe_ns = 0; e->pe_nsv = 0;
   } else if (!rgb_dev && e->rgb_override) {   // back to render.cmap: the prefixes as they were (the per-env pictures are drawn again)
-    e->n_static = e->kept_n_static; e->pe_ns = e->kept_pe_ns; e->pe_nsv = e->kept_pe_nsv;
+    for (int k = 0; k < e->n_views; ++k) e->views[k].n_static = e->views[k].kept_n_static;
+    e->pe_ns = e->kept_pe_ns; e->pe_nsv = e->kept_pe_nsv;
     if (e->pe_ns > 0 && e->pe_valid) HIPCHK(hipMemset(e->pe_valid, 0, sizeof(int32_t) * (size_t)e->n_envs));
   }
   e->rgb_override = rgb_dev;
@@ -1273,14 +1448,15 @@ int moog_engine_env_prefix(moog_engine_t* e, int32_t* n_slots) {
 
 int moog_engine_static_prefix(moog_engine_t* e, int32_t* n_slots, uint8_t* image_dev, void* hip_stream) {
   if (!e) return fail(MOOG_E_INVALID, "null engine");
-  if (n_slots) *n_slots = e->n_static;
-  if (image_dev && e->n_static > 0) {
+  const RView& v = e->views[0];
+  if (n_slots) *n_slots = v.n_static;
+  if (image_dev && v.n_static > 0) {
     HIPCHK(hipSetDevice(e->device));
-    if (e->aa > 1) return fail(MOOG_E_UNSUPPORTED, "the cached picture of an anti-aliased renderer is canvas sized");
-    if (e->pad_w != e->canvas_w)
-      moog_crop_launch(e->s_bg, image_dev, (size_t)e->canvas_h, e->pad_w * 3, e->canvas_w * 3, (hipStream_t)hip_stream);
+    if (v.aa > 1) return fail(MOOG_E_UNSUPPORTED, "the cached picture of an anti-aliased renderer is canvas sized");
+    if (v.pad_w != v.canvas_w)
+      moog_crop_launch(v.s_bg, image_dev, (size_t)v.canvas_h, v.pad_w * 3, v.canvas_w * 3, (hipStream_t)hip_stream);
     else
-      HIPCHK(hipMemcpyAsync(image_dev, e->s_bg, (size_t)e->prog.render.width * e->prog.render.height * 3,
+      HIPCHK(hipMemcpyAsync(image_dev, v.s_bg, (size_t)v.render.width * v.render.height * 3,
                             hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
   }
   return MOOG_OK;

@@ -161,6 +161,8 @@ void moog_resize_launch(const RResize& r, const uint8_t* canvas, uint8_t* tmp, u
 int moog_raster_configure_mask(size_t lds_bytes);   // the same for the mask rasteriser's kernels
 int moog_raster_configure(size_t lds_bytes);   // hipFuncSetAttribute(max dynamic LDS); returns a hipError_t
 void moog_raster_launch(const RArgs& a, size_t lds_bytes, hipStream_t stream);
+// the draw records of n_em (<= MOOG_MAX_VIEWS) views, derived from the records of `a` (P, L, f64, i32, vinfo, n_envs, env0) in one launch
+void moog_derive_launch(const RmEmit* em, int n_em, const RArgs& a, hipStream_t stream);
 // Per-env prefix check: one wavefront per env compares the first n_static slots of the live record (alive bit, vertex count,
 // opacity, colour, live vertices) with the env's snapshot.  Different, or no picture yet (valid[env] == 0): the record is
 // copied to the snapshot, build[env] = 1, valid[env] = 1; equal: build[env] = 0.  A change in the middle of an episode

@@ -1,19 +1,35 @@
 // moog_raster.hip -- the rasteriser kernel (see moog_raster.h for the design), its own
 // translation unit so that it builds independently of the step / reset kernels.
+#include <mutex>
+
 #include "moog_raster_kernel.h"
 #include "moog_raster_mask.h"
 
 template <int WORDS>
 __global__ __launch_bounds__(R_THREADS, 6) void moog_raster_kernel(RArgs a) { raster_block<WORDS>(a, (int)blockIdx.x, -1); }
 
-int moog_raster_configure_mask(size_t lds_bytes) { return moog_raster_mask_configure(lds_bytes); }
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per kernel function, i.e. for the whole process: the value only ever
+// grows, so that an engine (or view) created later with a smaller plan does not lower the limit under an earlier one's launches.
+static std::mutex g_lds_mu;
+static size_t g_span_lds = 0, g_mask_lds = 0;
+
+int moog_raster_configure_mask(size_t lds_bytes) {
+  std::lock_guard<std::mutex> lock(g_lds_mu);
+  if (lds_bytes <= g_mask_lds) return (int)hipSuccess;
+  const int err = moog_raster_mask_configure(lds_bytes);
+  if (err == (int)hipSuccess) g_mask_lds = lds_bytes;
+  return err;
+}
 
 int moog_raster_configure(size_t lds_bytes) {
+  std::lock_guard<std::mutex> lock(g_lds_mu);
+  if (lds_bytes <= g_span_lds) return (int)hipSuccess;
   hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(moog_raster_kernel<1>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
   if (err == hipSuccess)
     err = hipFuncSetAttribute(reinterpret_cast<const void*>(moog_raster_kernel<2>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+  if (err == hipSuccess) g_span_lds = lds_bytes;
   return (int)err;
 }
 
@@ -29,14 +45,22 @@ static RmArgs mask_args(const RArgs& r) {
   return a;
 }
 
+// The draw records of n_em views (each RmEmit names its own output) from the records `a` points at: one launch.
+void moog_derive_launch(const RmEmit* em, int n_em, const RArgs& a, hipStream_t stream) {
+  RmDeriveArgs d;
+  memset(&d, 0, sizeof d);
+  for (int k = 0; k < n_em && k < MOOG_MAX_VIEWS; ++k) d.em[k] = em[k];
+  d.n_em = n_em < MOOG_MAX_VIEWS ? n_em : MOOG_MAX_VIEWS;
+  d.P = a.P; d.L = a.L; d.f64 = a.f64; d.i32 = a.i32; d.vinfo = a.vinfo; d.n_envs = a.n_envs; d.env0 = a.env0;
+  moog_draw_derive_launch(d, stream);
+}
+
 // Ordinary frames of programs the mask rasteriser takes (RmSetup::ok) are drawn by it; the pictures of the static / per-env
 // prefix, frames on top of a per-env prefix and every other program's frames by the push / sort / span kernel.
 void moog_raster_launch(const RArgs& a, size_t lds_bytes, hipStream_t stream) {
   if (a.ms.ok && !a.build && a.sbg_env_stride == 0 && !a.env_build) {
     if (!a.draw_ready) {   // records the engine did not step itself: the emitter on the records in HBM
-      RmDeriveArgs d;
-      d.em = a.em; d.P = a.P; d.L = a.L; d.f64 = a.f64; d.i32 = a.i32; d.vinfo = a.vinfo; d.n_envs = a.n_envs; d.env0 = a.env0;
-      moog_draw_derive_launch(d, stream);
+      moog_derive_launch(&a.em, 1, a, stream);
     }
     moog_raster_mask_launch(mask_args(a), a.ms.lds, stream);
     return;

@@ -68,18 +68,24 @@ __global__ __launch_bounds__(RM_THREADS, RM_WAVES_PER_SIMD) void moog_raster_mas
 }
 
 // The draw records of frames the engine did not step itself (moog_engine_render after load_state or an edit of the state
-// tensors, resets, programs whose step kernels do not emit): one wavefront per env runs the emitter on the record in HBM.
-struct RmDeriveArgs { RmEmit em; const moog_program_t* P; moog_layout_t L; const double* f64; const int32_t* i32; const uint32_t* vinfo; int32_t n_envs; int32_t env0; };
+// tensors, resets, programs whose step kernels do not emit, the extra views of moog_engine_add_view): one wavefront per env
+// runs the emitter on the record in HBM, once per view -- the primary's and every extra view's records in one launch.
+struct RmDeriveArgs { RmEmit em[MOOG_MAX_VIEWS]; const moog_program_t* P; moog_layout_t L; const double* f64; const int32_t* i32; const uint32_t* vinfo; int32_t n_envs; int32_t env0; int32_t n_em; };
 __global__ __launch_bounds__(64) void moog_draw_derive_kernel(RmDeriveArgs d) {
   const int env = (int)blockIdx.x;
   if (env >= d.n_envs) return;
   RmSrcRecord src;
   src.P = d.P; src.L = &d.L; src.f = d.f64 + (size_t)env * d.L.f64_per_env; src.q = d.i32 + (size_t)env * d.L.i32_per_env; src.vi = d.vinfo;
-  RmEmit em = d.em;
-  if (em.rgb_override) em.rgb_override += (size_t)d.env0 * em.slots;   // (the override array is indexed by the engine's env; a chunk of envs starts at env0)
-  RmEmitScratch sc;
-  rm_emit_scratch(reinterpret_cast<int32_t*>(moog_lds), em.slots, em.ncopy, &sc);
-  rm_emit(em, src, env, (int)threadIdx.x, sc, d.L.TOTV);
+#pragma unroll   // (constant indices: the views' arguments stay in the kernel argument segment, no private copy to index)
+  for (int k = 0; k < MOOG_MAX_VIEWS; ++k) {
+    if (k >= d.n_em) break;
+    if (k > 0) __syncthreads();   // (the views share the scratch: the previous emitter is done with it)
+    RmEmit em = d.em[k];
+    if (em.rgb_override) em.rgb_override += (size_t)d.env0 * em.slots;   // (the override array is indexed by the engine's env; a chunk of envs starts at env0)
+    RmEmitScratch sc;
+    rm_emit_scratch(reinterpret_cast<int32_t*>(moog_lds), em.slots, em.ncopy, &sc);
+    rm_emit(em, src, env, (int)threadIdx.x, sc, d.L.TOTV);
+  }
 }
 
 typedef void (*moog_raster_mask_fn)(RmArgs);
@@ -106,7 +112,12 @@ static inline void moog_raster_mask_launch(const RmArgs& a, size_t lds_bytes, hi
 }
 
 static inline void moog_draw_derive_launch(const RmDeriveArgs& d, hipStream_t stream) {
-  hipLaunchKernelGGL(moog_draw_derive_kernel, dim3((unsigned)d.n_envs), dim3(64), 4u * (size_t)RM_EMIT_SCRATCH_WORDS(d.em.slots, d.em.S, d.em.ncopy), stream, d);
+  size_t words = 0;   // dynamic LDS: the largest view's scratch (a torus view has nine items per slot)
+  for (int k = 0; k < d.n_em; ++k) {
+    const size_t w = (size_t)RM_EMIT_SCRATCH_WORDS(d.em[k].slots, d.em[k].S, d.em[k].ncopy);
+    if (w > words) words = w;
+  }
+  hipLaunchKernelGGL(moog_draw_derive_kernel, dim3((unsigned)d.n_envs), dim3(64), 4u * words, stream, d);
 }
 
 #endif  // MOOG_RASTER_MASK_H_

@@ -26,7 +26,10 @@ from .state_initialization import distributions as distribs
 
 Compiled = collections.namedtuple(
     'Compiled', ['program', 'layer_names', 'layer_slots', 'observer_key', 'layout', 'shape_names', 'rule_ref_index',
-                 'pstate_slots', 'dynamic_meta', 'color_fn', 'layer_n_init'])
+                 'pstate_slots', 'dynamic_meta', 'color_fn', 'layer_n_init', 'views'])
+# views: [(observer key, moog_render_t)] of the config's PILRenderers after the first, in dict order -- the engine's extra views
+# (moog_engine_add_view); never part of the program.  observer_key: the first PILRenderer's key, or None when the config has
+# none (the program's render is then 0 x 0: no frames).
 
 
 class _ShapeTable(object):
@@ -1319,24 +1322,47 @@ def compile_config(state_initializer, physics, task, action_space, observers, ga
     obs_items = list(observers.items()) if observers else []
     renderers = [(k, o) for k, o in obs_items if isinstance(o, observers_lib.PILRenderer)]
     others = [o for _, o in obs_items if not isinstance(o, (observers_lib.PILRenderer, observers_lib.RawState))]
-    if len(renderers) != 1 or others:
-        raise NotImplementedError('exactly one PILRenderer observer is supported')
-    obs_key, ren = renderers[0]
-    Rn = P.render
-    Rn.width, Rn.height = int(ren._image_size[0]), int(ren._image_size[1])
-    Rn.aa = int(ren._anti_aliasing)   # the canvas is aa x the observation (pil_renderer.py:64-66)
-    Rn.cmap = _abi.MOOG_CMAP_HSV if ren._cmap == 'hsv' else _abi.MOOG_CMAP_IDENTITY
-    if isinstance(ren._polygon_modifier, polygon_modifiers.TorusGeometry):
-        Rn.polymod = _abi.MOOG_POLYMOD_TORUS
-    elif isinstance(ren._polygon_modifier, polygon_modifiers.FirstPersonAgent):
-        Rn.polymod = _abi.MOOG_POLYMOD_FIRST_PERSON
-        Rn.polymod_layer = layer_index(ren._polygon_modifier._agent_layer)
-    elif isinstance(ren._polygon_modifier, polygon_modifiers.DoNothing):
-        Rn.polymod = _abi.MOOG_POLYMOD_NONE
-    else:
-        raise NotImplementedError('polygon modifier %r' % (type(ren._polygon_modifier).__name__,))
-    for c in range(3):
-        Rn.bg[c] = int(ren._bg_color[c])
+    if others:
+        raise NotImplementedError('observers other than PILRenderer and RawState are not lowered (%s)'
+                                  % (', '.join(sorted(set(type(o).__name__ for o in others))),))
+    if len(renderers) > _abi.MOOG_MAX_VIEWS:
+        raise NotImplementedError('at most %d PILRenderer observers per config (MOOG_MAX_VIEWS), got %d'
+                                  % (_abi.MOOG_MAX_VIEWS, len(renderers)))
+
+    def lower_render(Rn, ren):
+        Rn.width, Rn.height = int(ren._image_size[0]), int(ren._image_size[1])
+        Rn.aa = int(ren._anti_aliasing)   # the canvas is aa x the observation (pil_renderer.py:64-66)
+        Rn.cmap = _abi.MOOG_CMAP_HSV if ren._cmap == 'hsv' else _abi.MOOG_CMAP_IDENTITY
+        if isinstance(ren._polygon_modifier, polygon_modifiers.TorusGeometry):
+            Rn.polymod = _abi.MOOG_POLYMOD_TORUS
+        elif isinstance(ren._polygon_modifier, polygon_modifiers.FirstPersonAgent):
+            Rn.polymod = _abi.MOOG_POLYMOD_FIRST_PERSON
+            Rn.polymod_layer = layer_index(ren._polygon_modifier._agent_layer)
+        elif isinstance(ren._polygon_modifier, polygon_modifiers.DoNothing):
+            Rn.polymod = _abi.MOOG_POLYMOD_NONE
+        else:
+            raise NotImplementedError('polygon modifier %r' % (type(ren._polygon_modifier).__name__,))
+        for c in range(3):
+            Rn.bg[c] = int(ren._bg_color[c])
+
+    # The first PILRenderer is the program's render (the primary); each further one an extra view of the engine, kept beside
+    # the program.  No renderer: render 0 x 0, a program that draws no frames.
+    obs_key, ren = renderers[0] if renderers else (None, None)
+    if ren is not None:
+        lower_render(P.render, ren)
+    color_fn = ren.color_to_rgb if ren is not None and ren._cmap == 'callable' else None
+    views = []
+    for key, other in renderers[1:]:
+        # The engine's colour override (moog_engine_set_color_override) holds the callable's colours and applies to every
+        # view: with a callable on the first renderer, every further one must use that very callable (and none can have one
+        # of its own).
+        if (other._cmap == 'callable' or color_fn is not None) and other.color_to_rgb is not color_fn:
+            raise NotImplementedError('PILRenderer %r: a color_to_rgb callable is supported on the first PILRenderer only; '
+                                      'when it has one, every further PILRenderer must use that very callable object'
+                                      % (key,))
+        Rv = _abi.Render()
+        lower_render(Rv, other)
+        views.append((key, Rv))
 
     # ---- vertex-count limits of the device kernels ------------------------------------------
     # Polygons of up to 128 vertices are integrated, moved and rasterised (the annulus of
@@ -1391,7 +1417,7 @@ def compile_config(state_initializer, physics, task, action_space, observers, ga
                  [(slot_of[id(sp)], key, cell, table) for sp, key, cell, table in getattr(tr, 'dynamic_meta', [])
                   if id(sp) in slot_of],
                  # PILRenderer(color_to_rgb=<a callable>): evaluated on the host (environment.py _refresh_colors)
-                 ren.color_to_rgb if ren._cmap == 'callable' else None, layer_n_init)
+                 color_fn, layer_n_init, views)
     # shape id -> Sprite.shape value (sprite.py:517-523): the name, or 'custom' for raw vertices
     c.shape_names.extend(k[1] if k[0] == 'name' else 'custom' for k, _ in shapes.entries)
     return c

@@ -4,7 +4,9 @@
 (`reset`, `step`, `observation`, `observation_spec`, `action_spec`,
 `state`-like accessors) with a leading env axis: step_type int32[N], reward
 float64[N] (NaN where the reference returns None), discount float64[N],
-observation {'image': uint8[N,H,W,3]} -- all torch tensors on the device.
+observation {'image': uint8[N,H,W,3]} -- all torch tensors on the device; a config with several
+PILRenderers gets one such tensor per renderer key (the engine's extra views), one with none only
+its RawState entries.
 Auto-reset follows environment.py:100-101 per env: the call after a LAST
 timestep ignores that env's action and returns a FIRST timestep.
 
@@ -103,11 +105,21 @@ class BatchedEnvironment(object):
         self.layout = L
         n = self.num_envs
         if _buffers is not None:
-            (self.state_f64, self.state_i32, self.reward, self.discount, self.step_type, self.image) = _buffers
+            (self.state_f64, self.state_i32, self.reward, self.discount, self.step_type, self.image) = _buffers[:6]
+            self.view_images = _buffers[6] if len(_buffers) > 6 else None
         else:
             with torch.cuda.device(self.device):
                 (self.state_f64, self.state_i32, self.reward, self.discount, self.step_type,
                  self.image) = self.allocate_buffers(torch, L, P, n, self.device)
+            self.view_images = None
+        if self.view_images is None:
+            with torch.cuda.device(self.device):
+                self.view_images = self.allocate_view_buffers(torch, self.compiled, n, self.device)
+        # frames per PILRenderer key, in the config's order: the primary's `image` and the extra views' tensors
+        self._frames = {}
+        if self.compiled.observer_key is not None:
+            self._frames[self.compiled.observer_key] = self.image
+        self._frames.update(self.view_images)
         self._handle = ctypes.c_void_p()
         if self._specialize:
             from . import _spec
@@ -121,11 +133,13 @@ class BatchedEnvironment(object):
         view.f64 = ctypes.cast(self.state_f64.data_ptr(), ctypes.POINTER(ctypes.c_double))
         view.i32 = ctypes.cast(self.state_i32.data_ptr(), ctypes.POINTER(ctypes.c_int32))
         _engine.check(self._lib, self._lib.moog_engine_load_state(self._handle, ctypes.byref(view)))
+        self._attach_views()
         self._out = _abi.StepOut()
         self._out.reward = ctypes.cast(self.reward.data_ptr(), ctypes.POINTER(ctypes.c_double))
         self._out.discount = ctypes.cast(self.discount.data_ptr(), ctypes.POINTER(ctypes.c_double))
         self._out.step_type = ctypes.cast(self.step_type.data_ptr(), ctypes.POINTER(ctypes.c_int32))
-        self._out.image = ctypes.cast(self.image.data_ptr(), ctypes.POINTER(ctypes.c_uint8))
+        if self.compiled.observer_key is not None:   # (no PILRenderer: the program draws no frames, the calls pass none)
+            self._out.image = ctypes.cast(self.image.data_ptr(), ctypes.POINTER(ctypes.c_uint8))
         self._composite = hasattr(action_space, 'action_spaces')
         self._n_actions = max(1, int(P.n_actions))
         self._is_grid = (not self._composite) and P.action.kind == _abi.MOOG_ACTION_GRID
@@ -140,6 +154,24 @@ class BatchedEnvironment(object):
         self._action_f32 = False
         self._apply_reset_pool()
         self._setup_color_fn()
+
+    def _attach_views(self):
+        """The config's PILRenderers after the first: an extra view of the engine each (moog_engine_add_view), drawing into
+        its own tensor whenever the primary's frames are drawn."""
+        self._view_index = {}
+        for key, render in self.compiled.views:
+            idx = ctypes.c_int32()
+            with self._torch.cuda.device(self.device):
+                _engine.check(self._lib, self._lib.moog_engine_add_view(self._handle, ctypes.byref(render), ctypes.byref(idx)))
+            _engine.check(self._lib, self._lib.moog_engine_set_view_image(
+                self._handle, idx.value, ctypes.c_void_p(self.view_images[key].data_ptr())))
+            self._view_index[key] = idx.value
+
+    @staticmethod
+    def allocate_view_buffers(torch, compiled, n, device):
+        """{key: uint8 [n, H, W, 3]} for the extra views (the config's PILRenderers after the first)."""
+        return {key: torch.zeros((n, int(R.height), int(R.width), 3), dtype=torch.uint8, device=device)
+                for key, R in compiled.views}
 
     def _setup_color_fn(self):
         """PILRenderer(color_to_rgb=<a callable>): the callable is evaluated here, on the host, once per distinct colour
@@ -288,11 +320,17 @@ class BatchedEnvironment(object):
         _engine.check(self._lib, self._lib.moog_engine_step_kernel(self._handle, ctypes.byref(v)))
         return 'specialised' if v.value else 'generic'
 
-    def raster_path(self):
+    def raster_path(self, view_key=None):
         """Which rasteriser draws this engine's frames: 'mask' (csrc/moog_raster_mask_core.h) or 'spans'
-        (csrc/moog_raster_kernel.h) -- moog_engine_raster_path."""
+        (csrc/moog_raster_kernel.h) -- moog_engine_raster_path.  view_key: the PILRenderer observer's key (default: the
+        first renderer, the program's own frames; another key: that extra view's, moog_engine_view_raster_path)."""
         v = ctypes.c_int32()
-        _engine.check(self._lib, self._lib.moog_engine_raster_path(self._handle, ctypes.byref(v)))
+        if view_key is None or view_key == self.compiled.observer_key:
+            _engine.check(self._lib, self._lib.moog_engine_raster_path(self._handle, ctypes.byref(v)))
+        else:
+            if view_key not in self._view_index:
+                raise KeyError('%r is not a PILRenderer observer of this config' % (view_key,))
+            _engine.check(self._lib, self._lib.moog_engine_view_raster_path(self._handle, self._view_index[view_key], ctypes.byref(v)))
         return 'mask' if (v.value & 1) else 'spans'
 
     def draw_records(self):
@@ -338,7 +376,7 @@ class BatchedEnvironment(object):
             if isinstance(o, raw_state.RawState):
                 obs[key] = raw_state.StateView(self)
             else:
-                obs[key] = self.image
+                obs[key] = self._frames[key]
         return obs
 
 
@@ -495,6 +533,7 @@ class BatchedEnvironment(object):
             view.f64 = ctypes.cast(self.state_f64.data_ptr(), ctypes.POINTER(ctypes.c_double))
             view.i32 = ctypes.cast(self.state_i32.data_ptr(), ctypes.POINTER(ctypes.c_int32))
             _engine.check(self._lib, self._lib.moog_engine_load_state(self._handle, ctypes.byref(view)))
+            self._attach_views()
             if f32:
                 _engine.check(self._lib, self._lib.moog_engine_set_action_dtype(self._handle, 1))
         if had_schedule:
@@ -685,6 +724,8 @@ class BatchedEnvironment(object):
         self._poll_faults()
         if self._color_fn is not None:
             self._render_with_colors()
+            return self._observation()
+        if self.compiled.observer_key is None:   # (no PILRenderer: nothing to draw)
             return self._observation()
         with self._torch.cuda.device(self.device):
             _engine.check(self._lib, self._lib.moog_engine_render(
@@ -884,12 +925,14 @@ class SubBatchedEnvironment(object):
         with torch.cuda.device(self.device):
             bufs = BatchedEnvironment.allocate_buffers(torch, L, P, self.num_envs, self.device)
             self._streams = [torch.cuda.Stream(device=self.device) for _ in range(G)]
+            self.view_images = BatchedEnvironment.allocate_view_buffers(torch, self.compiled, self.num_envs, self.device)
         (self.state_f64, self.state_i32, self.reward, self.discount, self.step_type, self.image) = bufs
         m = self.num_envs // G
         self.part_envs = m
         self.parts = []
         for g in range(G):
-            views = tuple(b[g * m:(g + 1) * m] for b in bufs)
+            views = tuple(b[g * m:(g + 1) * m] for b in bufs) + (
+                {k: t[g * m:(g + 1) * m] for k, t in self.view_images.items()},)
             self.parts.append(BatchedEnvironment(
                 state_initializer, physics, task, action_space, observers, game_rules, None,
                 num_envs=m, device=self.device, seed=seed, env_index0=int(env_index0) + g * m,
@@ -945,7 +988,16 @@ class SubBatchedEnvironment(object):
                 cur.wait_event(ev)
 
     def _timestep(self):
-        return dm_env.TimeStep(self.step_type, self.reward, self.discount, {'image': self.image})
+        from .observers import raw_state
+        obs = {}
+        for key, o in self.observers.items():   # every observer, in the config's order (as BatchedEnvironment._observation)
+            if isinstance(o, raw_state.RawState):
+                obs[key] = raw_state.StateView(self)
+            elif key == self.compiled.observer_key:
+                obs[key] = self.image
+            else:
+                obs[key] = self.view_images[key]
+        return dm_env.TimeStep(self.step_type, self.reward, self.discount, obs)
 
     def reset(self):
         for g in range(self.sub_batches):
@@ -993,6 +1045,9 @@ class SubBatchedEnvironment(object):
 
     def field(self, name):
         return BatchedEnvironment.field(self, name)
+
+    def sprites(self, env=0):
+        return BatchedEnvironment.sprites(self, env)
 
     def close(self):
         self._torch.cuda.synchronize(self.device)
