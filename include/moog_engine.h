@@ -27,7 +27,12 @@
 extern "C" {
 #endif
 
-#define MOOG_ABI_VERSION 30
+#define MOOG_ABI_VERSION 31
+/* What moog_program_t::abi_version holds: the version of the program blob's own format.  It moves only when the struct does
+ * (not with every new entry point: ABI 31 added moog_engine_set_action_repeat and left the blob alone), so that the programs'
+ * bytes -- and with them their hashes and the names of the specialised step kernels -- stay put. */
+#define MOOG_PROGRAM_VERSION 30
+#define MOOG_MAX_ACTION_REPEAT 64 /* moog_engine_set_action_repeat: env-steps one call takes at most */
 
 /* ---- capacity limits of the program blob -------------------------------- */
 #define MOOG_MAX_LAYERS 16
@@ -734,6 +739,16 @@ int moog_engine_step(moog_engine_t* e, const void* actions_dev,
  * `self._scaling_factor * action` is a float32 product (numpy: the Python float is the weak operand); the engine then
  * computes exactly that.  Grid actions stay int32; SetPosition components read the same buffer and use the values as they are. */
 int moog_engine_set_action_dtype(moog_engine_t* e, int32_t float32);
+/* Action repeat ("frame skip"): from the next moog_engine_step on, an env that is not being reset takes up to k env-steps per
+ * call (1 <= k <= MOOG_MAX_ACTION_REPEAT; 1 = the default), all with the call's action and each one a whole
+ * Environment.step (environment.py:98-126: rules, action, physics updates, step_count, task), inside one launch of the step
+ * kernel with its record on chip.  It stops after the first step m <= k whose task asks for a reset.  Outputs: reward =
+ * ((r_1 + r_2) + ...) + r_m in float64; step_type LAST / discount 0 when step m asked for a reset, else MID / 1; the frames
+ * show the state after step m; `count_dev` (int32[n_envs], borrowed, may be NULL) receives m, and 0 for the envs the call
+ * reset instead (their reset_next was set: FIRST, no env-step, exactly as with k = 1).  The records after the call equal,
+ * word for word, those after m calls with k = 1.  A fault does not end the repeat.  A call with injected uniforms
+ * (moog_inject_t: a per-call stream) is refused while k > 1. */
+int moog_engine_set_action_repeat(moog_engine_t* e, int32_t k, int32_t* count_dev);
 /* env.physics.step(env.state) only (tests/runtime_benchmark.py:101-107). */
 int moog_engine_physics_only(moog_engine_t* e, const moog_inject_t* inject,
                              void* hip_stream);

@@ -126,6 +126,8 @@ struct moog_engine {
   hipEvent_t ev_pool = nullptr;    // the call a fill follows
   int64_t pool_fills = 0;          // fill launches so far
   int act_f32 = 0;               // moog_engine_set_action_dtype: the action buffer holds float32 values
+  int action_repeat = 1;         // moog_engine_set_action_repeat: env-steps per call of moog_engine_step
+  int32_t* repeat_count = nullptr;   // [n_envs] the env-steps each env took in the call (caller-owned, or null)
   int32_t* layer_hw = nullptr;   // [2 * MOOG_MAX_LAYERS]: high-water mark / dropped appends of the dynamic layers
   TimedKernel timed[MOOG_K_COUNT];
   int32_t* fault_flag = nullptr;   // pinned host word the kernels OR fault bits into
@@ -364,7 +366,7 @@ static int validate_render(const moog_program_t* p, const moog_render_t* r) {
 
 static int validate(const moog_program_t* p) {
   if (!p) return fail(MOOG_E_INVALID, "null program");
-  if (p->abi_version != MOOG_ABI_VERSION) return fail(MOOG_E_INVALID, "program abi_version mismatch");
+  if (p->abi_version != MOOG_PROGRAM_VERSION) return fail(MOOG_E_INVALID, "program abi_version mismatch");
   if (p->n_slots < 0 || p->n_slots > MOOG_MAX_SLOTS) return fail(MOOG_E_INVALID, "n_slots out of range");
   if (p->n_layers < 0 || p->n_layers > MOOG_MAX_LAYERS) return fail(MOOG_E_INVALID, "n_layers out of range");
   if (p->n_hdraws < 0 || p->n_hdraws > MOOG_MAX_HDRAWS) return fail(MOOG_E_INVALID, "n_hdraws out of range");
@@ -784,9 +786,11 @@ int moog_engine_create(const moog_program_t* prog, int32_t n_envs, int32_t devic
     if (rc) { free_engine(e); return rc; }
   }
   {
-    int (*const configure[6])(size_t) = {moog_configure_step_f3, moog_configure_step_f4, moog_configure_step_t3,
-                                         moog_configure_step_t4, moog_configure_step_m3, moog_configure_step_m4};
-    for (int v = 0; v < 6 && err == hipSuccess; ++v) err = (hipError_t)configure[v](e->step_lds);
+    int (*const configure[12])(size_t) = {moog_configure_step_f3, moog_configure_step_f4, moog_configure_step_t3,
+                                          moog_configure_step_t4, moog_configure_step_m3, moog_configure_step_m4,
+                                          moog_configure_step_f3r, moog_configure_step_f4r, moog_configure_step_t3r,
+                                          moog_configure_step_t4r, moog_configure_step_m3r, moog_configure_step_m4r};
+    for (int v = 0; v < 12 && err == hipSuccess; ++v) err = (hipError_t)configure[v](e->step_lds);
   }
   {
     const StepVariant sv = step_variant_of(prog);
@@ -922,6 +926,8 @@ static KArgs make_args(moog_engine* e, const void* actions, const moog_inject_t*
   a.fault_flag = e->fault_flag;
   a.layer_hw = e->layer_hw;
   a.act_f32 = e->act_f32;
+  a.repeat = mode == MODE_STEP ? e->action_repeat : 1;
+  a.repeat_count = mode == MODE_STEP ? e->repeat_count : nullptr;
   a.xstack_off = e->xstack_off;
   a.watch = (mode == MODE_STEP) ? e->watch : nullptr; a.watch_off = e->watch_off;
   a.fops = e->d_fops; a.n_fops = e->n_fops;
@@ -938,14 +944,17 @@ static KArgs make_args(moog_engine* e, const void* actions, const moog_inject_t*
 }
 
 static void launch_step(moog_engine* e, hipStream_t s, const KArgs& a) {
-  static const moog_step_launch_fn launch[6] = {moog_launch_step_f3, moog_launch_step_f4, moog_launch_step_t3,
-                                                moog_launch_step_t4, moog_launch_step_m3, moog_launch_step_m4};
+  // (the second six: the kernels with the action-repeat loop, for calls that take more than one env-step)
+  static const moog_step_launch_fn launch[12] = {moog_launch_step_f3, moog_launch_step_f4, moog_launch_step_t3,
+                                                 moog_launch_step_t4, moog_launch_step_m3, moog_launch_step_m4,
+                                                 moog_launch_step_f3r, moog_launch_step_f4r, moog_launch_step_t3r,
+                                                 moog_launch_step_t4r, moog_launch_step_m3r, moog_launch_step_m4r};
   if (e->spec_launch) {
     e->spec_launch(e->n_envs, e->step_lds, s, &a);
     return;
   }
   const bool full = e->maze_kernel && !e->late_reset;
-  launch[(full ? 4 : (e->dynamic_rules ? 2 : 0)) + (e->step_wps == 4 ? 1 : 0)](e->n_envs, e->step_lds, s, a);
+  launch[(a.repeat > 1 ? 6 : 0) + (full ? 4 : (e->dynamic_rules ? 2 : 0)) + (e->step_wps == 4 ? 1 : 0)](e->n_envs, e->step_lds, s, a);
 }
 
 // What the draw-record emitter needs (moog_draw_record.h): by value in the step kernel's and the derive kernel's arguments.
@@ -1172,6 +1181,8 @@ int moog_engine_step(moog_engine_t* e, const void* actions_dev, const moog_injec
   if (rc) return rc;
   if (!actions_dev) return fail(MOOG_E_INVALID, "null actions");
   if (out && out->image && e->frameless) return fail(MOOG_E_INVALID, FRAMELESS_MSG);
+  if (e->action_repeat > 1 && inject && inject->uniforms)
+    return fail(MOOG_E_UNSUPPORTED, "injected uniforms are one call's stream: they cannot feed the several env-steps of an action repeat (moog_engine_set_action_repeat(e, 1, ...) first)");
   hipStream_t s = (hipStream_t)hip_stream;
   // (envs whose episode ended in the previous call are reset inside the step kernel, environment.py:100-101)
   KArgs a = make_args(e, actions_dev, inject, out, MODE_STEP, nullptr);
@@ -1307,6 +1318,14 @@ int moog_engine_get_reset_pool(moog_engine_t* e, int32_t* enabled, int64_t* stat
 int moog_engine_set_action_dtype(moog_engine_t* e, int32_t float32) {
   if (!e) return fail(MOOG_E_INVALID, "null engine");
   e->act_f32 = float32 ? 1 : 0;
+  return MOOG_OK;
+}
+
+int moog_engine_set_action_repeat(moog_engine_t* e, int32_t k, int32_t* count_dev) {
+  if (!e) return fail(MOOG_E_INVALID, "null engine");
+  if (k < 1 || k > MOOG_MAX_ACTION_REPEAT) return fail(MOOG_E_INVALID, "action repeat out of range (1 .. MOOG_MAX_ACTION_REPEAT)");
+  e->action_repeat = k;
+  e->repeat_count = count_dev;
   return MOOG_OK;
 }
 

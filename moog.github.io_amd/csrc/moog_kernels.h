@@ -179,6 +179,8 @@ struct KArgs {
   int32_t rank0;         // launch rank of workgroup 0 (0; a launch split by rank was measured in round 5, profiles/r05_step_experiments.txt)
   const uint32_t* draw_vinfo;   // vertex slot -> sprite slot | index within the sprite << 8 (the emitter's)
   RmEmit draw;           // draw.out != null: a step (MODE_STEP) also writes the env's draw record (moog_draw_record.h) for the raster launch behind it
+  int32_t repeat;        // action repeat (moog_engine_set_action_repeat): env-steps a MODE_STEP call takes per env, >= 1
+  int32_t* repeat_count; // [n_envs] the env-steps the call took (0: the call reset the env instead), or null
 };
 
 enum { MODE_STEP = 0, MODE_PHYSICS = 1, MODE_RESET_MASK = 2, MODE_FILL = 3 };
@@ -614,6 +616,13 @@ __global__ __launch_bounds__(SCHED_THREADS) void moog_sched_kernel(const float* 
 
 #endif  // MOOG_DEFINE_RESET_KERNELS
 
+// lane 0's value of a double, wave uniform (two scalar registers)
+__device__ __forceinline__ double uni_f64(double x) {
+  const long long b = __double_as_longlong(x);
+  const unsigned lo = (unsigned)uni((int)b), hi = (unsigned)uni((int)(b >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
 // DYN = the program has rules that create / move / filter sprites at run time (CreateSprites,
 // ChangeLayer, VanishByFilter): that variant carries the reset path's sampler; the plain one
 // is what the benchmark configs run.
@@ -622,7 +631,10 @@ __global__ __launch_bounds__(SCHED_THREADS) void moog_sched_kernel(const float* 
 // scratch in the hot loops) is faster once LDS holds fewer than fifteen records per CU anyway.
 // One env's step (or auto-reset), one wavefront.
 // Returns true when the call reset the env (the reset path writes colours / opacities / shapes straight to HBM).
-template <bool DYN>
+// REPEAT = the instantiation carries the action-repeat loop (moog_engine_set_action_repeat with k > 1).  The loop in the
+// one-step kernels cost the headline 2.3 % at k = 1 (registers of the collision recursion went to scratch:
+// profiles/action_repeat.txt), so those compile the body as the straight line it was and the loop has kernels of its own.
+template <bool DYN, bool REPEAT>
 __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned char* lds, const int lane) {
   const long long t_sched = a.cost ? clock64() : 0;
   int32_t* gq = a.i32 + (size_t)env * a.L.i32_per_env;
@@ -641,7 +653,7 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
         // components out, chosen because the program needs them only to build an episode: the same program on the kernel
         // that carries everything steps 1.4 - 2.7 times slower, profiles/r04_variant_tax.txt).  The env is marked and left
         // as it is; the full reset kernel, launched behind this one, opens its episode and releases the pool's lock.
-        if (e.lane == 0) a.late_mask[env] = 1;
+        if (e.lane == 0) { a.late_mask[env] = 1; if (a.repeat_count) a.repeat_count[env] = 0; }
         return;
       }
       env_reset<DYN>(e);
@@ -652,6 +664,7 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
       if (a.reward) a.reward[env] = __builtin_nan("");
       if (a.discount) a.discount[env] = __builtin_nan("");
       if (a.step_type) a.step_type[env] = 0;
+      if (a.repeat_count) a.repeat_count[env] = 0;
 #ifdef MOOG_PROFILE   // tools/reset_profile.py: cycles of the reset and of one of its sections instead of NaN
       if ((a.dbg & 128) && a.discount) {
         a.discount[env] = (double)(clock64() - t_begin);
@@ -665,60 +678,75 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
     if (a.cost && e.lane == 0) a.cost[env] = moog_cost_ema((float)(clock64() - t_sched), a.cost[env]);
     return;
   }
-  { PROF_T0; bbox_build_all(e); PROF_ADD(e, 9); }
   PProg P = as_const_prog(a.P);
   const int K = uni(P->updates_per_env_step);
-  if (a.mode == MODE_PHYSICS) {
-    for (int k = 0; k < K; ++k) apply_physics<DYN>(e);
-    store_record(e, a.H, a.L, gf, gq, a.fault_flag);
-    return;
-  }
-  {
-  PROF_T0;
-  SEC(e, SEC_RULES);
-  // environment.py:98-126
-  const int n_rules = uni(P->n_rules);
-  for (int r = 0; r < n_rules; ++r)
-    if (P->rules[r].parent < 0) rule_step<DYN>(e, r);
-  const bool af32 = a.act_f32 != 0;
-  if (uni(P->n_actions) > 1) {   // composite.py:61-62: every sub-space, in keyword order
-    const int na = uni(P->n_actions);
-    for (int k = 0; k < na; ++k) {
-      double x, y;
-      if (af32) { const float* act = reinterpret_cast<const float*>(a.actions) + (size_t)2 * na * env; x = act[2 * k]; y = act[2 * k + 1]; }
-      else { const double* act = reinterpret_cast<const double*>(a.actions) + (size_t)2 * na * env; x = act[2 * k]; y = act[2 * k + 1]; }
-      action_step(e, k, x, y, (int)x, af32);
+  // Action repeat (moog_engine_set_action_repeat): up to a.repeat env-steps with the call's action, the record staying in LDS
+  // between them; the repeat ends with the first step whose task asks for a reset.  Everything a call derives from the record
+  // is derived again for every step (the boxes below), so step j computes what a launch of its own would.  Wave uniform:
+  // the count, the flag and the reward so far (lane 0's values, the ones the outputs have always held) live in scalar registers.
+  const int reps = REPEAT ? a.repeat : 1;
+  int done = 0, sr = 0;
+  double rsum = 0;
+  for (;;) {
+    if constexpr (REPEAT) { e.cell_tab_n = 0; e.cell_nw = 0; }   // (as bind_env leaves them)
+    { PROF_T0; bbox_build_all(e); PROF_ADD(e, 9); }
+    if (a.mode == MODE_PHYSICS) {
+      for (int k = 0; k < K; ++k) apply_physics<DYN>(e);
+      store_record(e, a.H, a.L, gf, gq, a.fault_flag);
+      return;
     }
-  } else {
-    double ax = 0, ay = 0;
-    int ga = 4;
-    if (P->action.kind == MOOG_ACTION_GRID) ga = reinterpret_cast<const int32_t*>(a.actions)[env];
-    else if (af32) {
-      ax = reinterpret_cast<const float*>(a.actions)[2 * env];
-      ay = reinterpret_cast<const float*>(a.actions)[2 * env + 1];
+    {
+    PROF_T0;
+    SEC(e, SEC_RULES);
+    // environment.py:98-126
+    const int n_rules = uni(P->n_rules);
+    for (int r = 0; r < n_rules; ++r)
+      if (P->rules[r].parent < 0) rule_step<DYN>(e, r);
+    const bool af32 = a.act_f32 != 0;
+    if (uni(P->n_actions) > 1) {   // composite.py:61-62: every sub-space, in keyword order
+      const int na = uni(P->n_actions);
+      for (int k = 0; k < na; ++k) {
+        double x, y;
+        if (af32) { const float* act = reinterpret_cast<const float*>(a.actions) + (size_t)2 * na * env; x = act[2 * k]; y = act[2 * k + 1]; }
+        else { const double* act = reinterpret_cast<const double*>(a.actions) + (size_t)2 * na * env; x = act[2 * k]; y = act[2 * k + 1]; }
+        action_step(e, k, x, y, (int)x, af32);
+      }
     } else {
-      ax = reinterpret_cast<const double*>(a.actions)[2 * env];
-      ay = reinterpret_cast<const double*>(a.actions)[2 * env + 1];
+      double ax = 0, ay = 0;
+      int ga = 4;
+      if (P->action.kind == MOOG_ACTION_GRID) ga = reinterpret_cast<const int32_t*>(a.actions)[env];
+      else if (af32) {
+        ax = reinterpret_cast<const float*>(a.actions)[2 * env];
+        ay = reinterpret_cast<const float*>(a.actions)[2 * env + 1];
+      } else {
+        ax = reinterpret_cast<const double*>(a.actions)[2 * env];
+        ay = reinterpret_cast<const double*>(a.actions)[2 * env + 1];
+      }
+      action_step(e, 0, ax, ay, ga, af32);
     }
-    action_step(e, 0, ax, ay, ga, af32);
+    PROF_ADD(e, 10);
+    }
+    { PROF_T0; for (int k = 0; k < K; ++k) apply_physics<DYN>(e); PROF_ADD(e, 6); }
+    SEC(e, SEC_TASK);
+    int sc = EQ(e)[EL(e).o_step_count] + 1;
+    wsync();
+    if (e.lane == 0) EQ(e)[EL(e).o_step_count] = sc;
+    wsync();
+    double rj;
+    { PROF_T0; rj = task_reward<DYN>(e, sc, &sr); PROF_ADD(e, 11); }
+    wsync();
+    if (!REPEAT || reps <= 1) { rsum = rj; done = 1; break; }   // (a single step: its reward and flag as they are)
+    sr = uni(sr);
+    rj = uni_f64(rj);
+    rsum = done == 0 ? rj : uni_f64(rsum + rj);   // ((r_1 + r_2) + ...) + r_m, in float64
+    if (++done >= reps || sr) break;
   }
-  PROF_ADD(e, 10);
-  }
-  { PROF_T0; for (int k = 0; k < K; ++k) apply_physics<DYN>(e); PROF_ADD(e, 6); }
-  SEC(e, SEC_TASK);
-  int sc = EQ(e)[EL(e).o_step_count] + 1;
-  wsync();
-  if (e.lane == 0) EQ(e)[EL(e).o_step_count] = sc;
-  wsync();
-  int sr = 0;
-  double r;
-  { PROF_T0; r = task_reward<DYN>(e, sc, &sr); PROF_ADD(e, 11); }
-  wsync();
   if (e.lane == 0) {
     if (sr) EQ(e)[EL(e).o_reset_next] = 1;
-    if (a.reward) a.reward[env] = r;
+    if (a.reward) a.reward[env] = rsum;
     if (a.discount) a.discount[env] = sr ? 0.0 : 1.0;
     if (a.step_type) a.step_type[env] = sr ? 2 : 1;
+    if (a.repeat_count) a.repeat_count[env] = done;
   }
   SEC(e, SEC_STORE);
   emit_draw_record(e, a, env);   // (before the record's stores: a wave waits once for its stores to drain, at its end)
@@ -733,7 +761,7 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
   }
 }
 
-template <bool DYN, int WPS, int VARIANT>   // VARIANT only names the instantiation (one per translation unit)
+template <bool DYN, int WPS, int VARIANT, bool REPEAT>   // VARIANT only names the instantiation (one per translation unit)
 // Every device function must end up inlined into this kernel: the env's descriptor (`Env`: pointers and the layout's offsets)
 // has to live in registers.  One function left out of line takes it by reference through scratch memory, ~1000 cycles per
 // access: round 4 measured this kernel at 1270 instead of 800 us the day the inliner's cost model left apply_physics out
@@ -774,7 +802,7 @@ __global__ __launch_bounds__(MOOG_STEP_THREADS, WPS) void moog_step_kernel(KArgs
     a.H = hot_layout(L);
   }
 #endif
-  step_env<DYN>(a, env, moog_lds, (int)threadIdx.x);
+  step_env<DYN, REPEAT>(a, env, moog_lds, (int)threadIdx.x);
 #ifdef MOOG_WATCH
   if (a.watch && threadIdx.x == 0) { int32_t* w = reinterpret_cast<int32_t*>(__builtin_assume_aligned(moog_lds + a.watch_off, 16)); __hip_atomic_store(w + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 #endif
@@ -782,7 +810,7 @@ __global__ __launch_bounds__(MOOG_STEP_THREADS, WPS) void moog_step_kernel(KArgs
 
 
 // ---- launch functions (one translation unit each, so that they compile in parallel) ------------------
-// variant = (dynamic rules ? 2 : 0) + (waves per SIMD == 4 ? 1 : 0)
+// variant = (dynamic rules ? 2 : 0) + (waves per SIMD == 4 ? 1 : 0); the ...r functions: the kernels with the action-repeat loop
 typedef void (*moog_step_launch_fn)(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 void moog_launch_step_f3(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 void moog_launch_step_f4(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
@@ -790,12 +818,24 @@ void moog_launch_step_t3(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 void moog_launch_step_t4(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 void moog_launch_step_m3(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 void moog_launch_step_m4(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
+void moog_launch_step_f3r(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
+void moog_launch_step_f4r(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
+void moog_launch_step_t3r(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
+void moog_launch_step_t4r(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
+void moog_launch_step_m3r(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
+void moog_launch_step_m4r(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 int moog_configure_step_f3(size_t lds);
 int moog_configure_step_f4(size_t lds);
 int moog_configure_step_t3(size_t lds);
 int moog_configure_step_t4(size_t lds);
 int moog_configure_step_m3(size_t lds);
 int moog_configure_step_m4(size_t lds);
+int moog_configure_step_f3r(size_t lds);
+int moog_configure_step_f4r(size_t lds);
+int moog_configure_step_t3r(size_t lds);
+int moog_configure_step_t4r(size_t lds);
+int moog_configure_step_m3r(size_t lds);
+int moog_configure_step_m4r(size_t lds);
 void moog_launch_reset_plain(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 void moog_launch_reset_full(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 int moog_configure_reset_plain(size_t lds);

@@ -368,7 +368,7 @@ def compile_config(state_initializer, physics, task, action_space, observers, ga
                    meta_state_initializer=None, layer_capacity=None, keep_sprite_factors=False):
     # meta_state lives on the host (environment.py keeps it for `ModifyMetaState`)
     P = _abi.Program()
-    P.abi_version = _abi.MOOG_ABI_VERSION
+    P.abi_version = _abi.MOOG_PROGRAM_VERSION   # (the blob's own format: include/moog_engine.h)
     if keep_sprite_factors:   # scale / aspect_ratio per sprite in the records (LoggingEnvironment)
         P.sprite_factors = 1
     shapes = _ShapeTable(P)

@@ -17,7 +17,7 @@ SYMBOLS = (
     'moog_engine_step', 'moog_engine_physics_only', 'moog_engine_render',
     'moog_engine_set_timing', 'moog_engine_kernel_time', 'moog_engine_set_schedule',
     'moog_engine_set_debug', 'moog_engine_static_prefix', 'moog_engine_poll_faults',
-    'moog_engine_layer_usage', 'moog_engine_set_action_dtype',
+    'moog_engine_layer_usage', 'moog_engine_set_action_dtype', 'moog_engine_set_action_repeat',
     'moog_engine_read_watch', 'moog_engine_set_reset_pool', 'moog_engine_get_reset_pool',
     'moog_engine_env_prefix', 'moog_engine_set_color_override',
     'moog_engine_kernel_variant', 'moog_engine_raster_path', 'moog_engine_read_draw_records', 'moog_program_step_kernel', 'moog_engine_step_kernel',
@@ -82,6 +82,7 @@ def load_library(path=None):
     lib.moog_engine_step_kernel.argtypes = [vp, ctypes.POINTER(i32)]
     lib.moog_engine_get_reset_pool.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i64)]
     lib.moog_engine_set_action_dtype.argtypes = [vp, i32]
+    lib.moog_engine_set_action_repeat.argtypes = [vp, i32, vp]
     lib.moog_engine_layer_usage.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     lib.moog_engine_set_debug.argtypes = [vp, i32, i32]
     lib.moog_engine_static_prefix.argtypes = [vp, ctypes.POINTER(i32), vp, vp]

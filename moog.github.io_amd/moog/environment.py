@@ -44,8 +44,15 @@ class BatchedEnvironment(object):
 
     def __init__(self, state_initializer, physics, task, action_space, observers, game_rules=(),
                  meta_state_initializer=None, num_envs=1, device=None, seed=0, env_index0=0,
-                 layer_capacity=None, keep_sprite_factors=False, reset_pool='auto', specialize=False, _compiled=None,
-                 _buffers=None):
+                 layer_capacity=None, keep_sprite_factors=False, reset_pool='auto', specialize=False, action_repeat=1,
+                 _compiled=None, _buffers=None):
+        # action_repeat: k env-steps per step() call with the call's action ("frame skip"), inside one launch of the step kernel
+        # (set_action_repeat; include/moog_engine.h moog_engine_set_action_repeat).  What cannot be repeated on the device is
+        # refused here, before anything touches it.
+        self._auto_capacity = layer_capacity == 'auto' or (isinstance(layer_capacity, dict) and bool(layer_capacity.get('auto')))
+        self._host_rules = [r for r in game_rules if getattr(r, 'host_side', False)]
+        self._meta_state_initializer = meta_state_initializer
+        self._action_repeat = self._check_action_repeat(action_repeat)
         import torch
         self._torch = torch
         self._lib = _engine.load_library()  # raises when the HIP extension is missing
@@ -71,7 +78,6 @@ class BatchedEnvironment(object):
         # layers are sized to what the batch has needed so far, high-water x 1.25 (fit_layer_capacity): a record holds every slot's
         # vertices, so roomy initial capacities cost envs per CU for the whole run otherwise (first_person_predators_prey at
         # {prey: 32, predators: 96}: one env per CU, 0.88 M env-steps/s; fitted: two, 1.6 M).  Growth on demand goes on afterwards.
-        self._auto_capacity = False
         self._fit_after, self._n_step_calls = 0, 0
         if layer_capacity == 'auto':
             self._auto_capacity, layer_capacity, self._fit_after = True, None, 128
@@ -96,8 +102,6 @@ class BatchedEnvironment(object):
         # `ModifyMetaState` rules (arbitrary Python, never sprites): one object for a batch of one, a list of
         # num_envs objects otherwise.  Those rules run in a host loop over the envs, and every step then reads the
         # auto-reset flags back (one device-to-host copy per step): convenient, not fast.
-        self._host_rules = [r for r in game_rules if getattr(r, 'host_side', False)]
-        self._meta_state_initializer = meta_state_initializer
         self._meta_state = None
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None \
             else torch.device(device)
@@ -107,11 +111,17 @@ class BatchedEnvironment(object):
         if _buffers is not None:
             (self.state_f64, self.state_i32, self.reward, self.discount, self.step_type, self.image) = _buffers[:6]
             self.view_images = _buffers[6] if len(_buffers) > 6 else None
+            self.repeat_count = _buffers[7] if len(_buffers) > 7 else None
         else:
             with torch.cuda.device(self.device):
                 (self.state_f64, self.state_i32, self.reward, self.discount, self.step_type,
                  self.image) = self.allocate_buffers(torch, L, P, n, self.device)
             self.view_images = None
+            self.repeat_count = None
+        if self.repeat_count is None:
+            # env-steps each env took in the last step() call: action_repeat, fewer where the episode ended inside the call,
+            # 0 where the call reset the env (a FIRST timestep) and after reset()
+            self.repeat_count = torch.zeros((n,), dtype=torch.int32, device=self.device)
         if self.view_images is None:
             with torch.cuda.device(self.device):
                 self.view_images = self.allocate_view_buffers(torch, self.compiled, n, self.device)
@@ -152,8 +162,45 @@ class BatchedEnvironment(object):
         self.check_faults = True
         self._cost = self._perm = None
         self._action_f32 = False
+        self._apply_action_repeat()
         self._apply_reset_pool()
         self._setup_color_fn()
+
+    def _check_action_repeat(self, k):
+        """k as an int, or the reason an engine like this one cannot repeat an action on the device."""
+        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= _abi.MOOG_MAX_ACTION_REPEAT:
+            raise ValueError('action_repeat must be an integer in 1 .. %d, got %r' % (_abi.MOOG_MAX_ACTION_REPEAT, k))
+        k = int(k)
+        if k == 1:
+            return k
+        if self._host_rules or self._meta_state_initializer is not None:
+            raise NotImplementedError(
+                'action_repeat=%d: host-side meta-state rules (ModifyMetaState / a meta_state_initializer) run in Python once per '
+                'step() call, the repeated env-steps run inside one kernel launch: the rules would miss %d of every %d env-steps '
+                '(call step() %d times instead)' % (k, k - 1, k, k))
+        if self._auto_capacity:
+            raise NotImplementedError(
+                "action_repeat=%d: layer_capacity='auto' grows a layer between calls, when its high-water mark comes within a "
+                "margin sized for ONE env-step of appends; %d env-steps per call can overflow it before the host looks "
+                "(pass layer_capacity={layer: slots}; env.layer_usage() reports the demand)" % (k, k))
+        return k
+
+    def _apply_action_repeat(self):
+        _engine.check(self._lib, self._lib.moog_engine_set_action_repeat(
+            self._handle, self._action_repeat, ctypes.c_void_p(self.repeat_count.data_ptr())))
+
+    @property
+    def action_repeat(self):
+        return self._action_repeat
+
+    def set_action_repeat(self, k):
+        """k env-steps per step() call from the next call on (1: the reference's one step per call).  Every env holds the
+        call's action for up to k env-steps inside one launch of the step kernel and stops at the first one that ends its
+        episode; the timestep carries the rewards' sum (float64, in step order), the last step's step_type / discount and the
+        frame after it; `repeat_count` says how many env-steps each env took.  The state after the call is, bit for bit, the
+        state after that many single calls."""
+        self._action_repeat = self._check_action_repeat(k)
+        self._apply_action_repeat()
 
     def _attach_views(self):
         """The config's PILRenderers after the first: an extra view of the engine each (moog_engine_add_view), drawing into
@@ -432,6 +479,9 @@ class BatchedEnvironment(object):
         Returns the new capacities ({} when nothing shrinks).  Results do not depend on capacities (a sprite keeps its layer
         and its place in the layer's list)."""
         import math
+        if self._action_repeat > 1:
+            raise NotImplementedError('fit_layer_capacity turns growth on demand on (layer_capacity=\'auto\'), whose margin is sized '
+                                      'for one env-step of appends per call: set_action_repeat(1) first')
         torch = self._torch
         P, L = self.compiled.program, self.layout
         use = self.layer_usage()
@@ -536,6 +586,7 @@ class BatchedEnvironment(object):
             self._attach_views()
             if f32:
                 _engine.check(self._lib, self._lib.moog_engine_set_action_dtype(self._handle, 1))
+            self._apply_action_repeat()
         if had_schedule:
             self.enable_cost_schedule(True)
         self._apply_reset_pool()
@@ -584,6 +635,10 @@ class BatchedEnvironment(object):
                 ctypes.byref(self._out if self._color_fn is None else self._out_noimg), self._stream()))
         if self._color_fn is not None:
             self._render_with_colors()
+        if mask_t is None:
+            self.repeat_count.zero_()
+        else:
+            self.repeat_count.masked_fill_(mask_t.bool(), 0)
         if self.check_faults:
             self.raise_faults()   # (a reset is rare and its sampler is where most faults come from: check at once)
         del keep, mask_t
@@ -592,6 +647,9 @@ class BatchedEnvironment(object):
 
     def step(self, action, injected_uniforms=None):
         torch = self._torch
+        if injected_uniforms is not None and self._action_repeat > 1:
+            raise NotImplementedError('injected_uniforms feed ONE env-step (a per-call stream); action_repeat=%d takes several per '
+                                      'call: set_action_repeat(1) for the injected calls' % self._action_repeat)
         self._poll_faults()
         if self._composite:
             a = self._pack_composite(action)
@@ -903,7 +961,7 @@ class SubBatchedEnvironment(object):
 
     def __init__(self, state_initializer, physics, task, action_space, observers, game_rules=(),
                  meta_state_initializer=None, num_envs=1, sub_batches=2, device=None, seed=0, env_index0=0,
-                 layer_capacity=None, keep_sprite_factors=False, reset_pool='auto'):
+                 layer_capacity=None, keep_sprite_factors=False, reset_pool='auto', action_repeat=1):
         import torch
         self._torch = torch
         if layer_capacity == 'auto' or (isinstance(layer_capacity, dict) and layer_capacity.get('auto')):
@@ -927,16 +985,18 @@ class SubBatchedEnvironment(object):
             self._streams = [torch.cuda.Stream(device=self.device) for _ in range(G)]
             self.view_images = BatchedEnvironment.allocate_view_buffers(torch, self.compiled, self.num_envs, self.device)
         (self.state_f64, self.state_i32, self.reward, self.discount, self.step_type, self.image) = bufs
+        with torch.cuda.device(self.device):   # (BatchedEnvironment.repeat_count, whole batch: every part writes its slice)
+            self.repeat_count = torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device)
         m = self.num_envs // G
         self.part_envs = m
         self.parts = []
         for g in range(G):
             views = tuple(b[g * m:(g + 1) * m] for b in bufs) + (
-                {k: t[g * m:(g + 1) * m] for k, t in self.view_images.items()},)
+                {k: t[g * m:(g + 1) * m] for k, t in self.view_images.items()}, self.repeat_count[g * m:(g + 1) * m])
             self.parts.append(BatchedEnvironment(
                 state_initializer, physics, task, action_space, observers, game_rules, None,
                 num_envs=m, device=self.device, seed=seed, env_index0=int(env_index0) + g * m,
-                reset_pool=reset_pool, _compiled=self.compiled, _buffers=views))
+                reset_pool=reset_pool, action_repeat=action_repeat, _compiled=self.compiled, _buffers=views))
         self.physics, self.task, self.action_space = physics, task, action_space
         self.observers, self.game_rules = observers, game_rules
         self._is_grid = self.parts[0]._is_grid
@@ -944,6 +1004,17 @@ class SubBatchedEnvironment(object):
 
     def stream(self, g):
         return self._streams[g]
+
+    @property
+    def action_repeat(self):
+        return self.parts[0].action_repeat
+
+    def set_action_repeat(self, k):
+        """BatchedEnvironment.set_action_repeat for every sub-batch (from each one's next queued call on)."""
+        for p in self.parts:
+            p._check_action_repeat(k)
+        for p in self.parts:
+            p.set_action_repeat(k)
 
     def part_slice(self, g):
         return slice(g * self.part_envs, (g + 1) * self.part_envs)
