@@ -144,6 +144,31 @@ int rm_model_frames(const moog_program_t* P, const double* f64, const int32_t* i
   return 0;
 }
 
+// Whether the engine draws this program's frames with the mask rasteriser (the host-side rule behind moog_engine_raster_path,
+// setup_view in moog_engine.hip, restated): a one-tile canvas (anti-aliasing included), polygons of at most RM_BIG_NV vertices,
+// at most 256 polygons (a torus has nine per sprite), and tables -- with the fewest row records a plan may have, a canvas
+// height, in the 16-byte or the 4-byte form of the edge records -- within 64 KB of LDS.  1 / 0; lds[0 / 1] (or null): those two plans' bytes.
+int rm_model_mask_path(const moog_program_t* P, long long* lds) {
+  moog_layout_t L;
+  moog_layout(P, &L);
+  const int aa = P->render.aa > 1 ? P->render.aa : 1;
+  const int canvas_w = aa * P->render.width, canvas_h = aa * P->render.height, pad_w = (canvas_w + 15) & ~15;
+  int maxv = 1;
+  for (int sl = 0; sl < P->n_slots; ++sl) if (P->slot_vcap[sl] > maxv) maxv = P->slot_vcap[sl];
+  const int ncopy = P->render.polymod == MOOG_POLYMOD_TORUS ? 9 : 1;
+  if (lds) lds[0] = lds[1] = -1;
+  if (!(pad_w <= 128 && canvas_h <= 128 && maxv <= RM_BIG_NV && P->n_slots >= 1 && P->n_slots * ncopy <= 256 && L.TOTV >= 1)) return 0;
+  const int S = P->n_slots * ncopy;
+  int ok = 0;
+  for (int compact = 0; compact < 2; ++compact) {
+    RmPlan plan;
+    rm_plan(S, L.TOTV * ncopy, pad_w, canvas_h, canvas_h, (S + 31) / 32, RM_THREADS / 64, maxv > RM_MAX_NV ? 1 : 0, &plan, compact);
+    if (lds) lds[compact] = (long long)plan.total;
+    if (plan.total <= 64u * 1024u) ok = 1;
+  }
+  return ok;
+}
+
 void rm_model_hist(long long* out) { for (int i = 0; i < 16; ++i) { out[i] = rm_hist[i]; rm_hist[i] = 0; } }
 
 }  // extern "C"

@@ -189,7 +189,19 @@ SHIPPED = ('pong', 'chase_avoid_torus', 'colliding_predators', 'functional_maze'
 
 def load_amd_config(name):
     """The five shipped configs come from the reference's own files; the scaled
-    variants from this repo's recipes, run against the reference package."""
+    variants from this repo's recipes, run against the reference package.
+    `<name>@<size>` (example_configs.load's form, functional_maze@128 = BASELINE.json configs[3]): the reference's
+    get_config takes no size, so its 'image' observer is replaced by a reference PILRenderer of the same arguments
+    (functional_maze.py:221-225: anti_aliasing=1, color_to_rgb='hsv_to_rgb') drawing size x size."""
+    name, _, size = name.partition('@')
+    if size:
+        assert name == 'functional_maze', 'the renderer arguments below are that file\'s'
+        from moog import observers as ref_observers
+        cfg = load_amd_config(name)
+        assert list(cfg['observers']) == ['image']
+        cfg['observers'] = {'image': ref_observers.PILRenderer(
+            image_size=(int(size), int(size)), anti_aliasing=1, color_to_rgb='hsv_to_rgb')}
+        return cfg
     if name in SHIPPED:
         return importlib.import_module('moog_demos.example_configs.' + name).get_config(0)
     if name in ('parallelogram_catch_l1', 'parallelogram_catch_l2'):   # moving pellets
@@ -400,6 +412,7 @@ def record_config(name, cfg, seed, n_calls, caps_by_layer, n_sub_steps=2):
     sub_calls = tuple(caps_by_layer.pop('__sub_calls__', ()))   # further calls whose sub-step states are recorded
     script = caps_by_layer.pop('__script__', None)   # (env, call, RandomState) -> action: a policy instead of random actions
     action_f32 = bool(caps_by_layer.pop('__action_f32__', False))   # hand the reference float32 actions (joystick.py:42-43)
+    n_sub_steps = caps_by_layer.pop('__n_sub_steps__', n_sub_steps)   # leading calls whose sub-step states are recorded (the bulk of a big recording)
     TAPE = Tape(seed)
     act_rs = np.random.RandomState(1000 + seed)
     env = environment.Environment(**cfg)
@@ -794,10 +807,14 @@ def main():
         ('colliding_predators', 48, {'__action_f32__': True}, (2,)),   # float32 actions: scaling_factor * action in float32
         ('chase_avoid_torus', 48, {'__action_f32__': True}, (2,)),
         ('functional_maze', 96, {'prey': 4}, (0, 1)),
+        ('functional_maze@128', 96, {'prey': 4}, (0, 1)),   # BASELINE.json configs[3]: another program than the 64 x 64 one
         ('falling_balls', 48, {}, (0,)),
         ('colliding_predators_32', 40, {}, (0,)),
+        ('colliding_predators_32', 64, {}, (1,)),   # the free-running window
+        ('colliding_predators_32', 64, {'__action_f32__': True}, (2,)),
         ('falling_balls_64', 12, {}, (0,)),
         ('falling_balls_64', 64, {'__skip__': 42, '__sub_calls__': (22, 23)}, (1,)),   # from the piled-up state of step 42, across the timeout at step 100
+        ('falling_balls_64', 32, {'__skip__': 75, '__n_sub_steps__': 0}, (2,)),   # deep in the pile, across the timeout at step 100 (no sub-step log: file size)
         ('forces_zoo', 96, {}, (0, 1)),
         ('chase_avoid_torus_l1', 48, {'prey': 2, 'predators': 2}, (0,)),
         ('tether_zoo_l0', 45, {}, (0,)),

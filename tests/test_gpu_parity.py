@@ -10,23 +10,7 @@ from helpers import compiled, fixture, records_from_fixture, state_diff
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
-RUNS = [('pong', 0), ('pong', 1), ('chase_avoid_torus', 0), ('chase_avoid_torus', 1),
-        ('colliding_predators', 0), ('colliding_predators', 1), ('colliding_predators', 2), ('chase_avoid_torus', 2), ('functional_maze', 0),
-        ('functional_maze', 1), ('falling_balls', 0), ('colliding_predators_32', 0),
-        ('falling_balls_64', 0), ('falling_balls_64', 1), ('forces_zoo', 0), ('forces_zoo', 1), ('chase_avoid_torus_l1', 0),
-        ('tether_zoo_l0', 0), ('tether_zoo_l1', 0), ('tether_zoo_l2', 0), ('tether_zoo_l3', 0),
-        ('tether_zoo_l4', 0), ('distrib_zoo', 0), ('distrib_zoo', 1),
-        ('rules_zoo_l0', 0), ('rules_zoo_l1', 0), ('rules_zoo_l1', 1),
-        ('lambda_zoo', 0), ('lambda_zoo', 1), ('rules_zoo_l2', 0),
-        ('first_person_predators_prey', 0), ('cond_zoo', 0), ('cond_zoo', 1), ('phase_zoo', 0), ('phase_zoo', 1), ('phase_zoo_l1', 0), ('phase_zoo_l1', 1), ('match_to_sample_l3', 0), ('match_to_sample_l3', 1), ('match_to_sample_l4', 0), ('match_to_sample_l2', 0), ('predators_arena_l2', 0), ('predators_arena_l2', 1), ('predators_arena_l1', 0), ('predators_arena_l3', 0), ('bounce_box_contact_prediction', 0), ('bounce_box_contact_prediction_l1', 0), ('red_green_l1', 0), ('red_green', 0), ('red_green_l3', 0), ('lookahead_zoo', 0), ('lookahead_zoo', 1), ('lookahead_zoo_l1', 0), ('lookahead_zoo_l1', 1), ('tracing_zoo', 0), ('tracing_zoo', 1), ('tracing_zoo_l1', 0), ('tracing_zoo_l1', 1), ('combo_zoo', 0), ('combo_zoo', 1),
-        ('actions_zoo', 0), ('actions_zoo', 1), ('actions_zoo_l1', 0), ('cleanup', 0), ('cleanup', 1),
-        ('aa_zoo', 0), ('aa_zoo_l1', 0), ('aa_zoo_l2', 0), ('aa_zoo_l3', 0), ('aa_zoo_l4', 0), ('aa_zoo_l5', 0), ('callables_zoo', 0), ('callables_zoo', 1), ('callables_zoo_l1', 0), ('callables_zoo_l2', 0), ('callables_zoo_l3', 0), ('callables_zoo_l3', 1), ('maze_zoo', 0), ('maze_zoo', 1), ('maze_zoo_l1', 0), ('maze_zoo_l2', 0), ('maze_zoo_l2', 1),
-        ('pacman', 0), ('pacman', 1), ('pacman_l1', 0),
-        ('sampler_zoo', 0), ('sampler_zoo', 1), ('sampler_zoo_l1', 0),
-        ('parallelogram_catch', 0), ('parallelogram_catch', 1), ('parallelogram_catch_l1', 0), ('parallelogram_catch_l1', 1),
-        ('parallelogram_catch_l2', 0), ('multi_tracking_with_feature_l3', 0), ('multi_tracking_with_feature_l3', 1),
-        ('multi_tracking_with_feature_l1', 0), ('dependent_zoo', 0), ('dependent_zoo', 1),
-        ('sampler_zoo_l2', 0), ('sampler_zoo_l2', 1), ('sampler_zoo_l3', 0), ('sampler_zoo_l3', 1)]
+RUNS = helpers.RUNS
 
 
 def make_env(name, n, seed=0, **kw):
@@ -58,15 +42,35 @@ def padded_uniforms(fx, ts):
     return u
 
 
-@pytest.mark.parametrize('name,seed', RUNS)
-def test_teacher_forced_vs_reference(name, seed):
+def expect_step_kernel(env, kernel):
+    """Fails unless `kernel` ('specialised' / 'generic', or None: whichever the engine picks) is the binary that steps `env`;
+    says which one it is."""
+    from moog import _spec
+    if kernel is None:
+        return
+    assert env.step_kernel() == kernel, (env.step_kernel(), _spec.path_of(env.compiled.program))
+    print('steps with the %s kernel%s' % (kernel, ': ' + os.path.basename(_spec.path_of(env.compiled.program))
+                                           if kernel == 'specialised' else ''))
+
+
+def select_step_kernel(monkeypatch, kernel):
+    """The environment in which the engine picks `kernel`: the specialised step kernels build() made (lib/spec), or none."""
+    if kernel == 'generic':
+        monkeypatch.setenv('MOOG_STEP_SPEC', '0')
+    else:
+        monkeypatch.delenv('MOOG_STEP_SPEC', raising=False)
+        monkeypatch.delenv('MOOG_SPEC_DIR', raising=False)
+
+
+def check_teacher_forced(name, seed, kernel=None):
     """All recorded calls at once: env i starts from the reference state of call
     i and must land on the reference state of call i+1 (floats <= 1e-5, ints,
-    rewards, step types and frames exact)."""
+    rewards, step types and frames exact).  Returns the worst float error."""
     c, fx = compiled(name), fixture(name, seed)
     T = len(fx['step_type'])
     ts = list(range(1, T))
     env = make_env(name, len(ts))
+    expect_step_kernel(env, kernel)
     L = c.layout
     f64 = np.zeros((len(ts), L.f64_per_env))
     i32 = np.zeros((len(ts), L.i32_per_env), np.int32)
@@ -89,19 +93,20 @@ def test_teacher_forced_vs_reference(name, seed):
         assert helpers.same_or_nan(float(out.discount[i]), fx['discount'][t]), t
         assert np.array_equal(img[i], fx['image'][t]), 'frame %d differs' % t
         assert int(q[i, L.o_fault]) == 0
-    print(name, seed, 'worst teacher-forced error vs reference', worst)
+    env.close()
+    return worst
 
 
-@pytest.mark.parametrize('name,seed', RUNS)
-def test_free_running_vs_reference(name, seed):
-    """One env free-running from the first reference state for <= 64 calls."""
+def check_free_running(name, seed, kernel=None):
+    """One env free-running from the first reference state for <= 64 calls.  Returns the worst float error."""
     c, fx = compiled(name), fixture(name, seed)
     env = make_env(name, 1)
-    import test_oracle_golden as tog
-    T = min([len(fx['step_type']), 65, tog.FREE_WINDOW.get((name, seed), 65)])
+    expect_step_kernel(env, kernel)
+    T = min([len(fx['step_type']), 65, helpers.FREE_WINDOW.get((name, seed), 65)])
     f64, i32 = records_from_fixture(fx, 0, c)
     upload(env, f64, i32)
     env.check_faults = False
+    worst = 0.0
     for t in range(1, T):
         a = helpers.action_of(fx, t)
         a = a.reshape((1,) + a.shape) if a.ndim == 2 else a.reshape((1, 2) if not fx['is_grid'] else (1,))
@@ -110,15 +115,111 @@ def test_free_running_vs_reference(name, seed):
         d = state_diff(fx, t, c, f, q)
         assert d['ints_ok'], (t, d)
         assert d['float'] <= TOL, (t, d)
+        worst = max(worst, d['float'])
         assert int(out.step_type[0]) == int(fx['step_type'][t])
         # (a reward that is a function of the float state -- Reset(reward_fn=lambda state: 10 * x + 1), callables_zoo --
         #  drifts with it: inside the same budget as the state; every other reward is exact)
         r, want = float(out.reward[0]), float(fx['reward'][t])
         assert helpers.same_or_nan(r, want) or abs(r - want) <= TOL * max(1.0, abs(want)), (t, r, want)
     assert np.array_equal(out.observation['image'][0].cpu().numpy(), fx['image'][T - 1])
+    env.close()
+    return worst
 
 
-@pytest.mark.parametrize('name,seed', [r for r in RUNS if r != ('falling_balls_64', 1)])   # (that recording starts at step 42)
+@pytest.mark.parametrize('name,seed', RUNS)
+def test_teacher_forced_vs_reference(name, seed):
+    """Every recorded call, teacher-forced (check_teacher_forced), on whichever step kernel the engine picks."""
+    print(name, seed, 'worst teacher-forced error vs reference', check_teacher_forced(name, seed))
+
+
+@pytest.mark.parametrize('name,seed', RUNS)
+def test_free_running_vs_reference(name, seed):
+    """One env free-running from the first reference state for <= 64 calls (check_free_running)."""
+    check_free_running(name, seed)
+
+
+BASELINE_RUNS = [r for r in RUNS if r[0] in helpers.BASELINE_PROGRAMS]
+BASELINE_BATCH = {'colliding_predators_32': 4096, 'falling_balls_64': 8192, 'functional_maze@128': 8192, 'chase_avoid_torus': 4096}
+
+
+@pytest.mark.parametrize('kernel', ['specialised', 'generic'])
+@pytest.mark.parametrize('name,seed', BASELINE_RUNS)
+def test_reference_recordings_on_both_step_kernels(name, seed, kernel, monkeypatch):
+    """The programs BASELINE.json measures, every recording of each, teacher-forced and free-running (the bodies and the bars of
+    the two tests above) on a NAMED step binary: the program-specialised kernel bench.py times (lib/spec/step_<hash>.so, built
+    by __graft_entry__.build() -- the test FAILS when the engine did not pick it up, so the parity claim is about that binary)
+    and the generic kernel of the same program (MOOG_STEP_SPEC=0).  functional_maze@128's frames here are the engine's
+    first 128 x 128 frames held against Pillow's."""
+    select_step_kernel(monkeypatch, kernel)
+    tf = check_teacher_forced(name, seed, kernel)
+    fr = check_free_running(name, seed, kernel)
+    print('%s seed %d on the %s kernel: worst error vs reference teacher-forced %.3g, free-running %.3g' % (name, seed, kernel, tf, fr))
+
+
+@pytest.mark.parametrize('name,seed', BASELINE_RUNS)
+def test_full_batch_teacher_forced_vs_reference(name, seed, monkeypatch):
+    """The batch BASELINE.json measures (4096 envs; 8192 for functional_maze@128 and falling_balls_64) filled by tiling the
+    recorded calls: with t(i) = 1 + i mod (T - 1), env i starts from the reference state of call t(i) - 1, gets the action and
+    the recorded uniforms of call t(i), and after one step() EVERY env equals the reference state of its call -- ints exact,
+    floats <= 1e-5, reward / discount / step type exact, fault word 0, frame bit-exact.  The comparison is per call: the
+    first env of a call against the recording (state_diff), every other env of that call against the first, bit for bit,
+    floats included -- which is also independence of batch position at full occupancy.  On the specialised kernel, with the
+    cost-sorted schedule bench.py runs under: the step is taken twice from the same states, the second time in the launch
+    order the first one's costs give (the full-batch raster launch and the second resident round of the step and raster
+    kernels are what a batch of this size adds to the small ones above)."""
+    import torch
+    select_step_kernel(monkeypatch, 'specialised')
+    c, fx = compiled(name), fixture(name, seed)
+    L = c.layout
+    T = len(fx['step_type'])
+    n = BASELINE_BATCH[name]
+    assert n > 2 * (T - 1)
+    call = 1 + np.arange(n) % (T - 1)          # t(i)
+    f1 = np.zeros((T - 1, L.f64_per_env))
+    q1 = np.zeros((T - 1, L.i32_per_env), np.int32)
+    for t in range(1, T):
+        records_from_fixture(fx, t - 1, c, f1, q1, env=t - 1)
+    f0, q0 = f1[call - 1], q1[call - 1]
+    actions = np.stack([helpers.action_of(fx, t) for t in range(1, T)])[call - 1]
+    uniforms = padded_uniforms(fx, list(range(1, T)))[call - 1]
+    env = make_env(name, n)
+    expect_step_kernel(env, 'specialised')
+    env.enable_cost_schedule()
+    env.check_faults = False
+    worst = 0.0
+    for rnd in range(2):
+        upload(env, f0, q0)
+        out = env.step(actions, injected_uniforms=uniforms)
+        f, q = download(env)
+        img = out.observation['image'].cpu().numpy()
+        step_type, reward, discount = out.step_type.cpu().numpy(), out.reward.cpu().numpy(), out.discount.cpu().numpy()
+        if rnd == 1:   # (the second launch went in the order of the first one's costs)
+            perm = env._perm.cpu().numpy()
+            assert sorted(perm.tolist()) == list(range(n))
+            assert float(env._cost.max()) > 0
+        for t in range(1, T):
+            idx = np.nonzero(call == t)[0]
+            i = int(idx[0])
+            d = state_diff(fx, t, c, f, q, env=i)
+            assert d['ints_ok'], (rnd, t, d)
+            assert d['float'] <= TOL, (rnd, t, d)
+            worst = max(worst, d['float'])
+            assert int(step_type[i]) == int(fx['step_type'][t]), (rnd, t)
+            assert helpers.same_or_nan(float(reward[i]), fx['reward'][t]), (rnd, t)
+            assert helpers.same_or_nan(float(discount[i]), fx['discount'][t]), (rnd, t)
+            assert np.array_equal(img[i], fx['image'][t]), 'frame of call %d differs (round %d)' % (t, rnd)
+            assert not q[idx, L.o_fault].any(), (rnd, t)
+            # every other env of this call: the same bits as the first
+            for what, a in (('int records', q), ('float records', f), ('frames', img), ('step types', step_type),
+                            ('rewards', reward), ('discounts', discount)):
+                same = (a[idx] == a[i]) | ((a[idx] != a[idx]) & (a[i] != a[i])) if a.dtype.kind == 'f' else a[idx] == a[i]
+                bad = idx[~same.reshape(len(idx), -1).all(axis=1)]
+                assert bad.size == 0, ('%s of envs that share call %d differ (round %d)' % (what, t, rnd), bad[:8].tolist(), int(bad.size))
+    env.close()
+    print('%s seed %d: %d envs over %d calls, worst error vs reference %.3g' % (name, seed, n, T - 1, worst))
+
+
+@pytest.mark.parametrize('name,seed', [r for r in RUNS if r not in helpers.MID_EPISODE_RUNS])   # (those start later in an episode)
 def test_reset_sampler_vs_reference(name, seed):
     """Device-side state initialisation replaying the reference's recorded draws."""
     c, fx = compiled(name), fixture(name, seed)
@@ -1731,7 +1832,7 @@ def test_raster_path_by_program():
     """Which rasteriser a program's frames take (moog_engine_raster_path): the mask rasteriser for one-tile frames of
     polygons with <= 128 vertices (the 102-vertex annuli take its cooperative row routine), the nine copies per sprite of a
     torus included; multi-tile frames (pacman 256 x 256) and frames whose tables outgrow 64 KB of LDS keep the span kernel."""
-    for name, want in (('colliding_predators_32', 'mask'), ('functional_maze', 'mask'), ('falling_balls_64', 'mask'),
+    for name, want in (('colliding_predators_32', 'mask'), ('functional_maze', 'mask'), ('functional_maze@128', 'mask'), ('falling_balls_64', 'mask'),
                        ('pacman', 'spans'), ('chase_avoid_torus', 'mask'), ('match_to_sample_l3', 'mask'),
                        ('first_person_predators_prey', 'mask')):
         env = make_env(name, 4, seed=1)
@@ -1742,6 +1843,19 @@ def test_raster_path_by_program():
             assert env.raster_compact_edges(), name
         if name in ('colliding_predators_32', 'functional_maze'):
             assert not env.raster_compact_edges(), name
+        env.close()
+
+
+def test_raster_path_rule_equals_the_engines():
+    """The CPU frame test (tests/test_raster_mask_model.py test_model_frames_vs_reference_frames) decides by a restated rule
+    (tests/csrc/raster_mask_model.cpp rm_model_mask_path) which programs' recorded frames go through the mask rasteriser's
+    model: for every program with a recording the engine itself must say the same (moog_engine_raster_path)."""
+    import test_raster_mask_model as trm
+    m = trm.build_model()
+    for name in sorted(set(r[0] for r in RUNS)):
+        env = make_env(name, 2, seed=1)
+        want = 'mask' if trm.mask_path(m, env.compiled) else 'spans'
+        assert env.raster_path() == want, (name, env.raster_path(), want)
         env.close()
 
 

@@ -23,6 +23,28 @@ def test_layout_matches_header():
     assert helpers.oracle().oracle_program_sizeof() == ctypes.sizeof(_abi.Program)
 
 
+def test_runs_list_equals_the_recordings_on_disk():
+    """helpers.RUNS -- the list the oracle tests and the HIP tests are parametrised by -- names every reference recording
+    in tests/golden and nothing else: a recording that is on disk but not in the list (or the other way round) would be
+    untested without anybody noticing.  The recordings with a test of their own are named in helpers, one by one."""
+    runs = list(helpers.RUNS)
+    assert len(set(runs)) == len(runs), 'an entry twice: %s' % sorted(r for r in set(runs) if runs.count(r) > 1)
+    disk = helpers.recordings_on_disk()
+    own = set(helpers.RECORDINGS_WITH_OWN_TESTS)
+    assert own <= set(disk), 'named as tested elsewhere but not on disk: %s' % sorted(own - set(disk))
+    assert not own & set(runs)
+    assert set(disk) - own == set(runs), ('on disk but not in RUNS: %s; in RUNS but not on disk: %s' % (
+        sorted(set(disk) - own - set(runs)), sorted(set(runs) - set(disk))))
+    # the recordings whose call 0 is no reset are the ones the reset-sampler test leaves out, and no others
+    mid = sorted(r for r in runs if int(helpers.fixture(*r)['step_type'][0]) != 0)
+    assert mid == sorted(helpers.MID_EPISODE_RUNS), mid
+    # every program BASELINE.json measures has recordings, and they are the programs build() specialises a step kernel for
+    import __graft_entry__ as entry
+    assert sorted(helpers.BASELINE_PROGRAMS) == sorted(entry.SPEC_WORKLOADS)
+    for name in helpers.BASELINE_PROGRAMS:
+        assert any(r[0] == name for r in runs), name
+
+
 def test_hip_library_exports_abi():
     """The C-ABI library loads and exports every symbol include/moog_engine.h declares."""
     lib = _engine.load_library()

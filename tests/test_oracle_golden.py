@@ -10,23 +10,7 @@ import pytest
 import helpers
 from helpers import OracleEnv, compiled, fixture, records_from_fixture, state_diff, uniforms_of
 
-RUNS = [('pong', 0), ('pong', 1), ('chase_avoid_torus', 0), ('chase_avoid_torus', 1),
-        ('colliding_predators', 0), ('colliding_predators', 1), ('colliding_predators', 2), ('chase_avoid_torus', 2), ('functional_maze', 0),
-        ('functional_maze', 1), ('falling_balls', 0), ('colliding_predators_32', 0),
-        ('falling_balls_64', 0), ('falling_balls_64', 1), ('forces_zoo', 0), ('forces_zoo', 1), ('chase_avoid_torus_l1', 0),
-        ('tether_zoo_l0', 0), ('tether_zoo_l1', 0), ('tether_zoo_l2', 0), ('tether_zoo_l3', 0),
-        ('tether_zoo_l4', 0), ('distrib_zoo', 0), ('distrib_zoo', 1),
-        ('rules_zoo_l0', 0), ('rules_zoo_l1', 0), ('rules_zoo_l1', 1),
-        ('lambda_zoo', 0), ('lambda_zoo', 1), ('rules_zoo_l2', 0),
-        ('first_person_predators_prey', 0), ('cond_zoo', 0), ('cond_zoo', 1), ('phase_zoo', 0), ('phase_zoo', 1), ('phase_zoo_l1', 0), ('phase_zoo_l1', 1), ('match_to_sample_l3', 0), ('match_to_sample_l3', 1), ('match_to_sample_l4', 0), ('match_to_sample_l2', 0), ('predators_arena_l2', 0), ('predators_arena_l2', 1), ('predators_arena_l1', 0), ('predators_arena_l3', 0), ('bounce_box_contact_prediction', 0), ('bounce_box_contact_prediction_l1', 0), ('red_green_l1', 0), ('red_green', 0), ('red_green_l3', 0), ('lookahead_zoo', 0), ('lookahead_zoo', 1), ('lookahead_zoo_l1', 0), ('lookahead_zoo_l1', 1), ('tracing_zoo', 0), ('tracing_zoo', 1), ('tracing_zoo_l1', 0), ('tracing_zoo_l1', 1), ('combo_zoo', 0), ('combo_zoo', 1),
-        ('actions_zoo', 0), ('actions_zoo', 1), ('actions_zoo_l1', 0), ('cleanup', 0), ('cleanup', 1),
-        ('aa_zoo', 0), ('aa_zoo_l1', 0), ('aa_zoo_l2', 0), ('aa_zoo_l3', 0), ('aa_zoo_l4', 0), ('aa_zoo_l5', 0), ('callables_zoo', 0), ('callables_zoo', 1), ('callables_zoo_l1', 0), ('callables_zoo_l2', 0), ('callables_zoo_l3', 0), ('callables_zoo_l3', 1), ('maze_zoo', 0), ('maze_zoo', 1), ('maze_zoo_l1', 0), ('maze_zoo_l2', 0), ('maze_zoo_l2', 1),
-        ('pacman', 0), ('pacman', 1), ('pacman_l1', 0),
-        ('sampler_zoo', 0), ('sampler_zoo', 1), ('sampler_zoo_l1', 0),
-        ('parallelogram_catch', 0), ('parallelogram_catch', 1), ('parallelogram_catch_l1', 0), ('parallelogram_catch_l1', 1),
-        ('parallelogram_catch_l2', 0), ('multi_tracking_with_feature_l3', 0), ('multi_tracking_with_feature_l3', 1),
-        ('multi_tracking_with_feature_l1', 0), ('dependent_zoo', 0), ('dependent_zoo', 1),
-        ('sampler_zoo_l2', 0), ('sampler_zoo_l2', 1), ('sampler_zoo_l3', 0), ('sampler_zoo_l3', 1)]
+RUNS = helpers.RUNS
 TOL = 1e-5   # BASELINE.json: float sprite state within 1e-5 abs
 
 
@@ -60,11 +44,7 @@ def test_teacher_forced_steps(name, seed):
     print(name, seed, 'worst teacher-forced error', worst)
 
 
-# (Round 2 limited the free-running window of the piled-up falling_balls_64 recording to 4 calls.  The divergence came
-#  from one thing: numpy evaluates np.dot / 1-D norms through OpenBLAS, whose ddot rounds the second product into the sum
-#  with a fused multiply-add.  With npdot2 / npnorm restated that way the recording is reproduced free-running for all 64
-#  calls with a worst error of 0.)
-FREE_WINDOW = {}
+FREE_WINDOW = helpers.FREE_WINDOW
 
 
 def knife_edge_calls(fx):

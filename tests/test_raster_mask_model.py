@@ -20,8 +20,7 @@ SO = os.path.join(BUILD, 'libraster_mask_model.so')
 _P = ctypes.POINTER
 
 
-@pytest.fixture(scope='module')
-def model():
+def build_model():
     os.makedirs(BUILD, exist_ok=True)
     hdr = os.path.join(helpers.REPO, 'include', 'moog_engine.h')
     draw = os.path.join(os.path.dirname(CORE), 'moog_draw_record.h')
@@ -31,6 +30,11 @@ def model():
                                '-Wno-unused-function', SRC, '-o', tmp])
         os.replace(tmp, SO)
     return ctypes.CDLL(SO)
+
+
+@pytest.fixture(scope='module')
+def model():
+    return build_model()
 
 
 def model_polygon(m, xy, W, H, mode, stats):
@@ -117,7 +121,7 @@ def test_model_vs_oracle_fuzz(model, seed):
     assert st[1] < 0.01 * st[0], ('rows sent to the generic routine', int(st[1]), int(st[0]))
 
 
-def model_frames(m, c, f64, i32, cap_rows, static=None, threads=128, compact=0):
+def model_frames(m, c, f64, i32, cap_rows, static=None, threads=128, compact=0, rgb_override=None):
     P = c.program
     n = f64.shape[0]
     W, H = (P.render.width + 15) & ~15, P.render.height
@@ -128,7 +132,8 @@ def model_frames(m, c, f64, i32, cap_rows, static=None, threads=128, compact=0):
     rc = m.rm_model_frames(ctypes.byref(P), f64.ctypes.data_as(dp), i32.ctypes.data_as(ip), n, img.ctypes.data_as(bp), threads,
                            cap_rows, ns, nsv, None if sf is None else sf.ctypes.data_as(dp),
                            None if sq is None else sq.ctypes.data_as(ip), None if sbg is None else sbg.ctypes.data_as(bp),
-                           None, st.ctypes.data_as(_P(ctypes.c_longlong)), compact)
+                           None if rgb_override is None else rgb_override.ctypes.data_as(_P(ctypes.c_uint32)),
+                           st.ctypes.data_as(_P(ctypes.c_longlong)), compact)
     assert rc == 0, rc
     return img[:, :, :P.render.width], st
 
@@ -162,6 +167,77 @@ def test_model_frames_vs_oracle(model, name, cap_rows):
         assert bad.size == 0, ('frames differ at step %d with compact edge records' % k, bad[:8].tolist())
     if cap_rows < 192 and name not in ('chase_avoid_torus', 'parallelogram_catch'):
         assert passes > 4 * n, 'the capped records were meant to force several passes per frame'
+
+
+def mask_path(m, c):
+    """The engine's own rule for which programs the mask rasteriser draws (tests/csrc/raster_mask_model.cpp rm_model_mask_path;
+    tests/test_gpu_parity.py test_raster_path_rule_equals_the_engines holds it against moog_engine_raster_path)."""
+    return bool(m.rm_model_mask_path(ctypes.byref(c.program), None))
+
+
+def left_out_of_the_frame_test(m, c):
+    """Why a program's recordings cannot go through model_frames (None: they can).  Structural reasons only."""
+    if not mask_path(m, c):
+        return 'span-path program (multi-tile canvas, or tables beyond 64 KB of LDS)'
+    if c.program.render.aa > 1:
+        return 'anti-aliasing: the model has no resize stage'
+    return None
+
+
+@pytest.mark.parametrize('name,seed', helpers.RUNS)
+def test_model_frames_vs_reference_frames(model, name, seed):
+    """The mask rasteriser's device code against the frames Pillow itself drew: every call of every reference recording whose
+    program takes the mask path (HSV colours, translucent sprites, torus copies, overlaps, 64 x 64 and 128 x 128), the
+    recorded state through the kernel's phases -- row records unlimited and as few as a plan may have (several passes per
+    frame), 16-byte and 4-byte edge records -- and the frame bit for bit equal to the recorded one.  No tolerance.  (Where
+    only the oracle's renderer stood between the kernel's algorithm and Pillow's frames before.)  A recording is left out
+    for a structural reason only, which is printed; none of the programs BASELINE.json measures may be."""
+    c, fx = helpers.compiled(name), helpers.fixture(name, seed)
+    why = left_out_of_the_frame_test(model, c)
+    if why is not None:
+        print('%s seed %d left out: %s' % (name, seed, why))
+        assert name not in helpers.BASELINE_PROGRAMS, (name, why)
+        return
+    P, L = c.program, c.layout
+    T = len(fx['step_type'])
+    f64 = np.zeros((T, L.f64_per_env))
+    i32 = np.zeros((T, L.i32_per_env), np.int32)
+    for t in range(T):
+        helpers.records_from_fixture(fx, t, c, f64, i32, env=t)
+    rgb = None
+    if getattr(c, 'color_fn', None) is not None:   # PILRenderer(color_to_rgb=<a callable>): evaluated on the host, as the engine does
+        o = helpers.OracleEnv(c, n_envs=T)
+        o.f64[:], o.i32[:] = f64, i32
+        rgb = np.ascontiguousarray(o._color_override())
+    ref = fx['image']
+    assert ref.shape == (T, P.render.height, P.render.width, 3), ref.shape
+    ncopy = 9 if P.render.polymod == _abi.MOOG_POLYMOD_TORUS else 1
+    unlimited = min(4096, int(P.n_slots) * ncopy * int(P.render.height))
+    passes = {}
+    for cap_rows in (unlimited, int(P.render.height)):
+        for compact in (0, 1):
+            img, st = model_frames(model, c, f64, i32, cap_rows, compact=compact, rgb_override=rgb)
+            bad = np.nonzero((img != ref).reshape(T, -1).any(axis=1))[0]
+            assert bad.size == 0, ('calls whose frame differs from the reference\'s (cap_rows %d, compact %d)' % (cap_rows, compact),
+                                   bad[:8].tolist(), int(bad.size), int((img[bad[0]] != ref[bad[0]]).any(axis=-1).sum()))
+            passes[cap_rows] = int(st[2])
+    print('%s seed %d: %d frames of %d x %d bit-exact; passes %s' % (name, seed, T, P.render.width, P.render.height, passes))
+
+
+def test_model_frames_vs_reference_frames_covers_the_baseline(model):
+    """What the frame test above leaves out, by program, and that the programs BASELINE.json measures are all in."""
+    out, kept = {}, set()
+    for name in sorted(set(r[0] for r in helpers.RUNS)):
+        why = left_out_of_the_frame_test(model, helpers.compiled(name))
+        if why is None:
+            kept.add(name)
+        else:
+            out[name] = why
+    for name, why in sorted(out.items()):
+        print('left out: %-36s %s' % (name, why))
+    assert set(helpers.BASELINE_PROGRAMS) <= kept, sorted(set(helpers.BASELINE_PROGRAMS) - kept)
+    sizes = set((helpers.compiled(n).program.render.width, helpers.compiled(n).program.render.height) for n in kept)
+    assert (128, 128) in sizes and (64, 64) in sizes, sizes
 
 
 def test_model_static_prefix(model):
