@@ -654,17 +654,17 @@ __device__ __forceinline__ int nth_set_bit32(unsigned m, int k) {
   return nth_set_bit16(hi ? m >> 16 : m & 0xffffu, hi ? k - c : k) + (hi ? 16 : 0);
 }
 
-#define CAND_SKIP 0xFFFF   // a candidate entry struck from the list (collision_same_layer): counts as rejected
+#define CAND_SKIP 0xFFFF   // no candidate (a group of lanes past the last pair of a batch): counts as rejected
 // G lanes per candidate: 16 (four candidates a batch).  G = 32 (two) for polygons of 17 - 32 vertices -- falling_balls_64's
 // 30-gons never fit sixteen lanes and each of its candidates takes the whole wave's path test -- is exact too, and was not
 // faster (profiles/r05_step_experiments.txt: falling_balls_64 +0.7 %, colliding_predators_32 -2 %).
+// `pr0`: the pair (s0 << 8 | s1) of this lane's group -- candidate k of the batch in the lanes of group k -- or CAND_SKIP.
 template <int G>
-__device__ inline int narrow_reject_prefix_g(const Env& e, int c, int n) {
+__device__ inline int narrow_reject_prefix_g(const Env& e, int pr0, int n) {
   constexpr int SH = G == 16 ? 4 : 5;
   constexpr unsigned long long GM = G == 16 ? 0xffffull : 0xffffffffull;
   const int grp = e.lane >> SH, gl = e.lane & (G - 1);
-  const int pr0 = grp < n ? (int)ECAND(e)[c + grp] : CAND_SKIP;
-  const bool active = pr0 != CAND_SKIP;
+  const bool active = (grp < n) & (pr0 != CAND_SKIP);
   const int pr = active ? pr0 : 0;
   const int s0 = pr >> 8, t = pr & 255;
   // (all the loads that depend only on the pair go out together: this routine is a chain of LDS round
@@ -734,8 +734,8 @@ __device__ inline int narrow_reject_prefix_g(const Env& e, int c, int n) {
   return r;
 }
 
-__device__ inline int narrow_reject_prefix(const Env& e, int c, int n) {
-  const int r = narrow_reject_prefix_g<16>(e, c, n);
+__device__ inline int narrow_reject_prefix(const Env& e, int pr0, int n) {
+  const int r = narrow_reject_prefix_g<16>(e, pr0, n);
   return r < 0 ? 0 : r;
 }
 
@@ -2157,8 +2157,8 @@ __device__ inline void collision_layer_pair(Env& e, const CollP& F, int a0, int 
       if (count - c >= 2 && !(e.dbg & (4 | 32))) {   // skip the leading candidates that do not overlap
         PROF_T0;
         SEC(e, SEC_BATCH);
-        const int n = count - c < 4 ? count - c : 4;
-        const int rr = uni(narrow_reject_prefix(e, c, n)), r = rr & 255;
+        const int n = count - c < 4 ? count - c : 4, grp = e.lane >> 4;
+        const int rr = uni(narrow_reject_prefix(e, grp < n ? (int)ECAND(e)[c + grp] : CAND_SKIP, n)), r = rr & 255;
 #ifdef MOOG_COUNT_PREFIX
         if (e.dbg & 128) { e.n_disj += 1 + 1000 * n; }
 #endif
@@ -2183,15 +2183,26 @@ __device__ inline void collision_layer_pair(Env& e, const CollP& F, int a0, int 
 // The same for a layer against itself (n <= 64 sprites), where the broad-phase test is symmetric: the
 // candidate pairs live in a bit matrix (row i = partners of sprite a0 + i), filled from the n (n - 1) / 2
 // unordered pairs (half the rounds of the ordered scan), and after a contact only the rows / columns of
-// the sprites it moved are re-tested (one round) instead of re-scanning every later pair.  The ordered
-// candidate list the narrow phase consumes is written from the matrix, rows in order, bits in order:
-// exactly the list the ordered scan would build.
+// the sprites it moved are re-tested (one round) instead of re-scanning every later pair.  Once filled, the
+// matrix lives in registers, lane r holding row r, and the narrow phase consumes it directly: a wave-uniform
+// cursor (row, column) walks the set bits, rows in order, bits in order -- the order in which the ordered scan
+// visits the pairs.
+// (Until the contact-path round the rows were written out after every contact as an ordered list in LDS -- a six-step
+//  prefix sum over the row counts and a loop of 16-bit stores per lane --, read back with one dependent LDS load per
+//  candidate, and scanned a second time to strike a mirrored pair.  The list had the cursor's order by construction:
+//  rows in order, bits in order.  profiles/step_contact_path.txt.)
 // (Tried in round 4 and dropped, both measured with tools/fn_bench.py: the matrix for two different layers -- the list
 //  builder's prefix sums cost the three small scans of the headline workload more than re-scanning after a contact,
 //  20.9 k cycles per sub-step against 18.9 k; and filling the matrix with lane = row sprite walking its partners -- fewer
 //  loads, but a dependent LDS round trip per partner instead of one per 64 pairs: 27.5 k.)
+__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int l) {   // l: wave uniform, 0 .. 63
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
 __device__ inline void collision_same_layer(Env& e, const CollP& F, int a0, int a1, int K) {
-  const int n = a1 - a0, total = n * n;
+  const int n = a1 - a0;
   const int symmetric = F.symmetric;
   unsigned long long* rowm = EROWM(e);
   wsync();
@@ -2214,6 +2225,8 @@ __device__ inline void collision_same_layer(Env& e, const CollP& F, int a0, int 
     }
   }
   wsync();
+  // lane r: row r (no bit at or above n; the lanes from n on hold no row), kept up to date by the re-test after a contact
+  unsigned long long row = e.lane < n ? rowm[e.lane] : 0ull;
   PROF_ADD(e, 4);
   // Lane r: the columns c for which the ordered pair (a0 + r, a0 + c) is known to change nothing -- its mirror image
   // (a0 + c, a0 + r) was visited earlier in this sub-step, overlapped in a pair of non-parallel edges and ended "future
@@ -2222,112 +2235,81 @@ __device__ inline void collision_same_layer(Env& e, const CollP& F, int a0, int 
   // four end "future contact", and a pair that overlaps without colliding does so twice in every sub-step.
   unsigned long long skipbits = 0ull;
   const bool use_skip = !uni(EP(e)->vel_alias);   // (velocity arrays shared across sprites: a contact elsewhere may touch the pair)
-  int start = 0;
-  while (start < total) {
-    // ---- the ordered list of candidates with flattened index >= start, as many whole rows as fit --------
-    PROF_T0;
+  // The cursor (wave uniform): every ordered pair before (a0 + crow, a0 + ccol) has been dealt with.  ccol < n <= 64.
+  int crow = 0, ccol = 0;
+  while (crow < n) {
+    // ---- the next candidates from the cursor on, four at the most: the set bits of row & ~skipbits ----
     SEC(e, SEC_LIST);
-    const int srow = div_small(start, n), scol = start - srow * n;
-    unsigned long long bits = 0ull;
-    if (e.lane < n && e.lane >= srow) {
-      bits = rowm[e.lane] & ~skipbits;
-      if (e.lane == srow) bits &= ~((1ull << scol) - 1ull);
-    }
-    const int cnt = __popcll(bits);
-    int inc = cnt;
-    for (int o = 1; o < 64; o <<= 1) {
-      const int tt = __shfl_up(inc, o);
-      if (e.lane >= o) inc += tt;
-    }
-    const unsigned long long over = __ballot(inc > CAND_CAP);
-    const int rows_end = over ? (__ffsll((long long)over) - 1) : 64;   // rows >= rows_end do not fit: next pass
-    int count = 0;
-    {
-      const int last = rows_end - 1 < 63 ? rows_end - 1 : 63;
-      count = rows_end > 0 ? __shfl(inc, last) : 0;
-      if (rows_end <= srow) {   // (a single row with more than CAND_CAP partners cannot happen: n <= 64 < CAND_CAP)
-        count = 0;
+    const unsigned long long live = row & ~skipbits;
+    unsigned long long rest = __ballot(live != 0ull) & ~((2ull << crow) - 1ull);   // the rows after crow that hold a candidate
+    unsigned long long b = readlane_u64(live, crow) & ~((1ull << ccol) - 1ull);    // what is left of row crow
+    int r = crow, nn = 0;
+    int p0 = CAND_SKIP, p1 = CAND_SKIP, p2 = CAND_SKIP, p3 = CAND_SKIP;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (b == 0ull && rest != 0ull) {
+        r = __ffsll((long long)rest) - 1;
+        rest &= rest - 1ull;
+        b = readlane_u64(live, r);   // (not empty: the ballot says so)
       }
-    }
-    if (e.lane < rows_end) {
-      int pos = inc - cnt;
-      unsigned long long b = bits;
-      while (b) {
+      if (b != 0ull) {
         const int j = __ffsll((long long)b) - 1;
         b &= b - 1ull;
-        ECAND(e)[pos++] = (uint16_t)(((a0 + e.lane) << 8) | (a0 + j));
+        const int pk = ((a0 + r) << 8) | (a0 + j);
+        if (k == 0) p0 = pk; else if (k == 1) p1 = pk; else if (k == 2) p2 = pk; else p3 = pk;
+        nn = k + 1;
       }
     }
-    const int scanned = rows_end >= n ? total : rows_end * n;
-    wsync();
-    PROF_ADD(e, 4);
+    if (nn == 0) break;   // none left
     // ---- consume ----------------------------------------------------------------------------
-    bool rebuilt = false;
-    // The mirror image (j, i) of a pair (i, j), i < j, that turned out to be a no-op both ways round is struck from the list
-    // (when the list reaches that far; `skipbits` keeps it out of later lists); a struck entry counts as rejected.
-    auto mark_mirror = [&](int s0k, int tk) {   // (s0k, tk): wave uniform, tk > s0k
-      const int j = tk - a0, i = s0k - a0;
-      if (e.lane == j) skipbits |= 1ull << i;
-      // struck from the list in hand, wherever it is: the lanes look at the (at most CAND_CAP = 128) entries together -- keeping
-      // the list builder's per-row offsets alive for this instead cost the kernels that carry the expression VM 200 VGPR spills
-      const int key = (tk << 8) | s0k;
-      for (int k = e.lane; k < count; k += 64)
-        if ((int)ECAND(e)[k] == key) ECAND(e)[k] = (uint16_t)CAND_SKIP;
-    };
-    for (int c = 0; c < count; ++c) {
-      bool known_hit = false, proper_hit = false;
-      SEC(e, SEC_CONSUME);
-      if (count - c >= 2 && !(e.dbg & (4 | 32))) {   // pass over the leading candidates that do not overlap
-        PROF_T0;
-        SEC(e, SEC_BATCH);
-        const int nn = count - c < 4 ? count - c : 4;
-        const int rr = uni(narrow_reject_prefix(e, c, nn)), r = rr & 255;
+    bool known_hit = false, proper_hit = false, rejected = false;
+    int pr = p0;
+    SEC(e, SEC_CONSUME);
+    if (nn >= 2 && !(e.dbg & (4 | 32))) {   // pass over the leading candidates that do not overlap
+      PROF_T0;
+      SEC(e, SEC_BATCH);
+      const int grp = e.lane >> 4;
+      const int rr = uni(narrow_reject_prefix(e, grp == 0 ? p0 : (grp == 1 ? p1 : (grp == 2 ? p2 : p3)), nn)), rj = rr & 255;
 #ifdef MOOG_COUNT_PREFIX   // (analysis builds: batches in the make_disjoint counter, tools/heavy_bench.py)
-        if (e.dbg & 128) { e.n_disj += 1 + 1000 * nn; }
+      if (e.dbg & 128) { e.n_disj += 1 + 1000 * nn; }
 #endif
-        SEC(e, SEC_CONSUME);
-        PROF_ADD(e, 8);
-        known_hit = (rr & 256) != 0;
-        proper_hit = (rr & 512) != 0;
-        c += r;
-        if (rr & 1024) { --c; continue; }   // all of them: on to the next batch
-      }
-      const int pr = uni((int)ECAND(e)[c]);
-      if (pr == CAND_SKIP) continue;
-      const int s0 = pr >> 8, t = pr & 255;
-      if (e.dbg & 4) continue;
-      bool noop = false;
-      if (collision_step(e, F, s0, t, K, known_hit, proper_hit, &noop)) {
-        start = (s0 - a0) * n + (t - a0) + 1;
-        // re-test the pairs of the sprites the contact moved (s0; t as well when symmetric)
-        PROF_T0;
-        SEC(e, SEC_RETEST);
-        for (int w = 0; w < (symmetric ? 2 : 1); ++w) {
-          const int m = (w ? t : s0) - a0;
-          wsync();
-          const bool cand = broad_pair(e, a0 + m, a0 + (e.lane < n ? e.lane : 0), e.lane < n);
-          const unsigned long long cm = __ballot(cand);
-          if (e.lane < n) {
-            unsigned long long rw = rowm[e.lane] & ~(1ull << m);
-            if (cand) rw |= 1ull << m;
-            rowm[e.lane] = (e.lane == m) ? cm : rw;
-          }
-          wsync();
-        }
-        // what was known about pairs of s0 or t is stale (position, velocity or angular velocity changed)
-        skipbits &= ~((1ull << (s0 - a0)) | (1ull << (t - a0)));
-        if (e.lane == s0 - a0 || e.lane == t - a0) skipbits = 0ull;
-        PROF_ADD(e, 4);
-        rebuilt = true;
-        break;
-      }
       SEC(e, SEC_CONSUME);
-      // nothing changed, and nothing would with the sprites exchanged: the mirror image (t, s0) comes later in this sub-step
-      if (noop && use_skip && t > s0 && !(e.dbg & 512)) { mark_mirror(s0, t); wsync(); }
+      PROF_ADD(e, 8);
+      rejected = (rr & 1024) != 0;   // all of them: the cursor passes the last one, on to the next batch
+      known_hit = (rr & 256) != 0;
+      proper_hit = (rr & 512) != 0;
+      const int at = rejected ? nn - 1 : rj;
+      pr = at == 0 ? p0 : (at == 1 ? p1 : (at == 2 ? p2 : p3));
     }
-    if (!rebuilt) start = scanned;
+    const int s0 = pr >> 8, t = pr & 255;
+    crow = s0 - a0; ccol = t - a0 + 1;   // the cursor passes (s0, t)
+    if (ccol >= n) { ++crow; ccol = 0; }
+    if (rejected || (e.dbg & 4)) continue;
+    bool noop = false;
+    if (collision_step(e, F, s0, t, K, known_hit, proper_hit, &noop)) {
+      // re-test the pairs of the sprites the contact moved (s0; t as well when symmetric): row and column m of the matrix
+      PROF_T0;
+      SEC(e, SEC_RETEST);
+      for (int w = 0; w < (symmetric ? 2 : 1); ++w) {
+        const int m = (w ? t : s0) - a0;
+        wsync();
+        const bool cand = broad_pair(e, a0 + m, a0 + (e.lane < n ? e.lane : 0), e.lane < n);
+        const unsigned long long cm = __ballot(cand);
+        if (e.lane < n) row = (e.lane == m) ? cm : (cand ? row | (1ull << m) : row & ~(1ull << m));
+      }
+      // what was known about pairs of s0 or t is stale (position, velocity or angular velocity changed)
+      skipbits &= ~((1ull << (s0 - a0)) | (1ull << (t - a0)));
+      if (e.lane == s0 - a0 || e.lane == t - a0) skipbits = 0ull;
+      PROF_ADD(e, 4);
+      continue;
+    }
+    SEC(e, SEC_CONSUME);
+    // nothing changed, and nothing would with the sprites exchanged: the mirror image (t, s0) comes later in this sub-step
+    // and is struck -- one bit of row t - a0
+    if (noop && use_skip && t > s0 && !(e.dbg & 512) && e.lane == t - a0) skipbits |= 1ull << (s0 - a0);
   }
 }
+
 
 // physics.py:88-117 (one substep).  DYN: the kernel variant that carries the rarely used components (here the maze
 // walk / MazePhysics, whose scratch frame must not weigh on the plain step kernel).
