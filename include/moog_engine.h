@@ -864,7 +864,9 @@ int moog_engine_kernel_variant(moog_engine_t* e, int32_t* variant, int32_t* late
  * program byte for byte (MOOG_STEP_SPEC=0: never).  An object that fails a check is reported on stderr and left alone.
  * moog_program_step_kernel (no device needed): the variant (0 plain, 1 + evaluator / sampler / dynamic layers, 2 + the rare
  * components), the register-allocation variant (waves per SIMD) and the hash the file name carries (FNV-1a 64 of the
- * program's bytes).  moog_engine_step_kernel: whether this engine steps with a specialised kernel. */
+ * program's bytes).  moog_engine_step_kernel: whether this engine steps with a specialised kernel (as things stand: a
+ * specialised kernel carries no profiling word, so while moog_engine_set_debug's step_debug is non-zero the engine steps
+ * with the generic kernels -- the same results -- and says so here). */
 int moog_program_step_kernel(const moog_program_t* program, int32_t* variant, int32_t* wps, uint64_t* hash);
 int moog_engine_step_kernel(moog_engine_t* e, int32_t* specialised);
 
@@ -895,7 +897,8 @@ int moog_engine_set_color_override(moog_engine_t* e, const uint32_t* rgb_dev);
 /* Profiling aids, both 0 in production (they make results wrong: timing only).  `step_debug`: bit
  * mask that switches parts of the step kernel off / writes cycle counters instead of outputs;
  * `raster_stop` = k truncates the raster kernel after phase k.  The initial values come from the
- * environment variables MOOG_STEP_DEBUG / MOOG_RASTER_STOP, read once by moog_engine_create. */
+ * environment variables MOOG_STEP_DEBUG / MOOG_RASTER_STOP, read once by moog_engine_create.  A non-zero
+ * `step_debug` is served by the generic step kernels (see moog_engine_step_kernel). */
 int moog_engine_set_debug(moog_engine_t* e, int32_t step_debug, int32_t raster_stop);
 
 /* Section sampling of the step kernel (a profiling aid; an engine created with the environment variable MOOG_WATCH=1 and a

@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "../../include/moog_engine.h"
+#include "moog_fops.h"   // FOp and the flattening (plain C++: the host, the tests and a specialised build share it)
 
 // The lowered config is read-only device memory.  Reading it through the constant
 // address space lets wave-uniform accesses compile to scalar loads (s_load, scalar
@@ -30,19 +31,6 @@ typedef const MOOG_CONST moog_rule_t* PRule;
 typedef const MOOG_CONST moog_task_t* PTask;
 typedef const MOOG_CONST moog_action_t* PAction;
 typedef const MOOG_CONST moog_shape_t* PShape;
-// One entry of the flattened force list: a (force, layer a, layer b) combination of physics.py:96-108 with everything its
-// loop header needs in 64 contiguous bytes (one scalar load), built once per engine on the host (moog_flatten_forces in
-// moog_kernels.h).  The nested loops over program.forces read ~10 dependent scalars per combination -- force kind, list
-// lengths, layer ids, slot ranges, the Collision parameters -- ten times per env-step: 6 % of the contact-heavy envs'
-// cycles and 12 % of the typical env's sat in those headers (profiles/r04_step_sections.txt).
-struct FOp {
-  int32_t fi, kind;          // index into program.forces (the rarely used kinds still read their record), MOOG_FORCE_*
-  int32_t a0, a1, b0, b1;    // slot ranges of the two layers (b0 = b1 = 0 for a one-layer force)
-  int32_t symmetric, i0, i1; // as in moog_force_t
-  int32_t n_b;               // 0: one-layer force
-  double p0, p1;
-  int32_t pad[2];
-};
 typedef const MOOG_CONST FOp* PFOp;
 typedef const MOOG_CONST moog_genop_t* PGenop;
 typedef const MOOG_CONST moog_factor_t* PFactor;
@@ -53,6 +41,12 @@ typedef const MOOG_CONST moog_factor_t* PFactor;
 // of 49 k and 7 % faster (profiles/r05_step_spec.txt).  The engine checks the embedded program against its own, byte for byte.
 #include MOOG_SPEC_PROGRAM_INC
 __device__ __forceinline__ PProg as_const_prog(const moog_program_t*) { return (PProg)&MOOG_SPEC_PROGRAM; }
+// The flattened force list is a pure function of the program, so it is a constant of the translation unit too (KArgs::fops /
+// n_fops are ignored): its length is an immediate and its entries sit in the object's constant data next to the program.
+// apply_physics reads it in a rolled loop.  One instantiation of the collision code per op (every field an immediate) was
+// measured and dropped: it does not fit the register file at three waves per SIMD (profiles/step_spec_fops.txt).
+static constexpr int MOOG_SPEC_NFOPS = moog_count_fops(MOOG_SPEC_PROGRAM);
+static constexpr FOpList<MOOG_SPEC_NFOPS> MOOG_SPEC_FOPS = moog_flatten_fops<MOOG_SPEC_NFOPS>(MOOG_SPEC_PROGRAM);
 #else
 __device__ __forceinline__ PProg as_const_prog(const moog_program_t* p) {
   return (PProg)(unsigned long long)p;
@@ -138,6 +132,9 @@ __device__ __forceinline__ moog_layout_t moog_spec_hot_layout_fn();   // (moog_k
 extern __shared__ __attribute__((aligned(16))) unsigned char moog_lds[];
 #define EL(e_) (moog_spec_hot_layout_fn())
 #define EP(e_) ((PProg)&MOOG_SPEC_PROGRAM)
+#define EFOP(e_, k) ((PFOp)&MOOG_SPEC_FOPS.op[k])
+#define ENFOPS(e_) (MOOG_SPEC_NFOPS)
+#define EDBG(e_) 0   // the profiling word: a specialised kernel carries none of it (the engine steps with the generic kernels when one is set)
 #define MOOG_SPEC_LDS_Q ((size_t)EL(0).f64_per_env * 8)
 #define MOOG_SPEC_LDS_BB (MOOG_SPEC_LDS_Q + (size_t)EL(0).i32_per_env * 4)
 #define MOOG_SPEC_LDS_VOFF (MOOG_SPEC_LDS_BB + (size_t)EL(0).S * 32)
@@ -152,6 +149,9 @@ extern __shared__ __attribute__((aligned(16))) unsigned char moog_lds[];
 #else
 #define EL(e_) ((e_).L)
 #define EP(e_) ((e_).P)
+#define EFOP(e_, k) (&(e_).fops[k])
+#define ENFOPS(e_) ((e_).n_fops)
+#define EDBG(e_) ((e_).dbg)
 #define EF(e_) ((e_).f)
 #define EQ(e_) ((e_).q)
 #define EBB(e_) ((e_).bb)
@@ -580,8 +580,8 @@ __device__ inline bool overlaps(const Env& e, int s0, int s1, bool prechecked = 
     if (circles_apart(e, s0, s1)) return false;
     if (bbox_apart(e, s0, s1)) return false;
   }
-  if (e.dbg & 8) return false;
-  if (e.dbg & 128) const_cast<Env&>(e).n_path++;
+  if (EDBG(e) & 8) return false;
+  if (EDBG(e) & 128) const_cast<Env&>(e).n_path++;
   PROF_T0;
   SEC(e, SEC_PATH);
   const bool hit = paths_intersect_filled(e, VERT(s0), NV(s0), VERT(s1), NV(s1), &BB(s0, 0), &BB(s1, 0), proper);
@@ -1053,7 +1053,7 @@ __device__ inline void directed_collision_vectors(const Env& e, int s0, int s1, 
   }
   uint64_t cmask = __ballot(contained);
   if (cmask == 0ull) return;
-  if (e.dbg & 32) return;
+  if (EDBG(e) & 32) return;
   double m[6];
   relative_motion_matrix(e, s0, s1, dt, m);
   // Rows of the crossing-coefficient matrix = contained vertices, visited in vertex order by
@@ -1111,7 +1111,7 @@ __device__ inline void directed_collision_vectors(const Env& e, int s0, int s1, 
     if (take) { ci = l; bv = dist; e1 = best; ca = bca; bpx = cpx; bpy = cpy; bsx = dfx; bsy = dfy; }
   }
   if (!anycross) return;   // `if not np.any(crossings)` (collisions.py:177-179)
-  if (e.dbg & 64) return;
+  if (EDBG(e) & 64) return;
   out.px = bpx; out.py = bpy;
   out.sx = bsx; out.sy = bsy;
   out.nx = out.ny = out.qx = out.qy = 0;
@@ -1257,7 +1257,7 @@ __device__ inline void directed_collision_vectors_pair(const Env& e, int sa, int
 // runs the same two directed searches and picks between them by the same two norms, compared the other way round.
 __device__ inline void get_collision_vectors(const Env& e, int s0, int s1, double dt, CVec& out, int* mirror_status = nullptr) {
   CVec r0, r1;
-  if (NV(s0) <= 32 && NV(s1) <= 32 && !(e.dbg & 64)) {
+  if (NV(s0) <= 32 && NV(s1) <= 32 && !(EDBG(e) & 64)) {
     directed_collision_vectors_pair(e, s0, s1, dt, r0, r1);
   } else {
     directed_collision_vectors(e, s1, s0, dt, r0);
@@ -1538,15 +1538,15 @@ __device__ inline bool collision_step(Env& e, const CollP& F, int s0, int s1, in
       if (mirror_noop && depth == 0) *mirror_noop = proper;   // no overlap, and none the other way round
       return moved;
     }
-    if (e.dbg & 16) return moved;
-    if (e.dbg & 128) e.n_resp++;
+    if (EDBG(e) & 16) return moved;
+    if (EDBG(e) & 128) e.n_resp++;
     double dt = 1. / K;
     CVec c;
     int mirror = CV_NONE;
     { PROF_T0; get_collision_vectors(e, s0, s1, dt, c, &mirror); PROF_ADD(e, 1); }
     if (c.status == CV_NONE) {
 #ifndef MOOG_COUNT_PREFIX
-      if (e.dbg & 128) e.n_disj++;
+      if (EDBG(e) & 128) e.n_disj++;
 #endif
       SEC(e, SEC_DISJOINT);
       PROF_T0; const bool dm = make_disjoint(e, s0, s1, symmetric); PROF_ADD(e, 2);
@@ -2154,13 +2154,13 @@ __device__ inline void collision_layer_pair(Env& e, const CollP& F, int a0, int 
     for (int c = 0; c < count; ++c) {
       bool known_hit = false;
       SEC(e, SEC_PAIR_CONSUME);
-      if (count - c >= 2 && !(e.dbg & (4 | 32))) {   // skip the leading candidates that do not overlap
+      if (count - c >= 2 && !(EDBG(e) & (4 | 32))) {   // skip the leading candidates that do not overlap
         PROF_T0;
         SEC(e, SEC_BATCH);
         const int n = count - c < 4 ? count - c : 4, grp = e.lane >> 4;
         const int rr = uni(narrow_reject_prefix(e, grp < n ? (int)ECAND(e)[c + grp] : CAND_SKIP, n)), r = rr & 255;
 #ifdef MOOG_COUNT_PREFIX
-        if (e.dbg & 128) { e.n_disj += 1 + 1000 * n; }
+        if (EDBG(e) & 128) { e.n_disj += 1 + 1000 * n; }
 #endif
         PROF_ADD(e, 8);
         SEC(e, SEC_PAIR_CONSUME);
@@ -2170,7 +2170,7 @@ __device__ inline void collision_layer_pair(Env& e, const CollP& F, int a0, int 
       }
       int pr = uni((int)ECAND(e)[c]);
       int s0 = pr >> 8, t = pr & 255;
-      if (!(e.dbg & 4) && collision_step(e, F, s0, t, K, known_hit)) {
+      if (!(EDBG(e) & 4) && collision_step(e, F, s0, t, K, known_hit)) {
         start = (s0 - a0) * nB + (t - b0) + 1;
         rebuilt = true;
         break;
@@ -2265,13 +2265,13 @@ __device__ inline void collision_same_layer(Env& e, const CollP& F, int a0, int 
     bool known_hit = false, proper_hit = false, rejected = false;
     int pr = p0;
     SEC(e, SEC_CONSUME);
-    if (nn >= 2 && !(e.dbg & (4 | 32))) {   // pass over the leading candidates that do not overlap
+    if (nn >= 2 && !(EDBG(e) & (4 | 32))) {   // pass over the leading candidates that do not overlap
       PROF_T0;
       SEC(e, SEC_BATCH);
       const int grp = e.lane >> 4;
       const int rr = uni(narrow_reject_prefix(e, grp == 0 ? p0 : (grp == 1 ? p1 : (grp == 2 ? p2 : p3)), nn)), rj = rr & 255;
 #ifdef MOOG_COUNT_PREFIX   // (analysis builds: batches in the make_disjoint counter, tools/heavy_bench.py)
-      if (e.dbg & 128) { e.n_disj += 1 + 1000 * nn; }
+      if (EDBG(e) & 128) { e.n_disj += 1 + 1000 * nn; }
 #endif
       SEC(e, SEC_CONSUME);
       PROF_ADD(e, 8);
@@ -2284,7 +2284,7 @@ __device__ inline void collision_same_layer(Env& e, const CollP& F, int a0, int 
     const int s0 = pr >> 8, t = pr & 255;
     crow = s0 - a0; ccol = t - a0 + 1;   // the cursor passes (s0, t)
     if (ccol >= n) { ++crow; ccol = 0; }
-    if (rejected || (e.dbg & 4)) continue;
+    if (rejected || (EDBG(e) & 4)) continue;
     bool noop = false;
     if (collision_step(e, F, s0, t, K, known_hit, proper_hit, &noop)) {
       // re-test the pairs of the sprites the contact moved (s0; t as well when symmetric): row and column m of the matrix
@@ -2306,7 +2306,7 @@ __device__ inline void collision_same_layer(Env& e, const CollP& F, int a0, int 
     SEC(e, SEC_CONSUME);
     // nothing changed, and nothing would with the sprites exchanged: the mirror image (t, s0) comes later in this sub-step
     // and is struck -- one bit of row t - a0
-    if (noop && use_skip && t > s0 && !(e.dbg & 512) && e.lane == t - a0) skipbits |= 1ull << (s0 - a0);
+    if (noop && use_skip && t > s0 && !(EDBG(e) & 512) && e.lane == t - a0) skipbits |= 1ull << (s0 - a0);
   }
 }
 
@@ -2317,14 +2317,14 @@ template <bool DYN>
 __device__ __forceinline__ void apply_physics(Env& e) {   // (forced: see the note at moog_step_kernel)
   PProg P = EP(e);
   const int K = uni(P->updates_per_env_step);
-  const int n_fops = e.n_fops;
+  const int n_fops = ENFOPS(e);
   for (int k = 0; k < n_fops; ++k) {
     SEC(e, SEC_FORCES);
-    PFOp op = &e.fops[k];
+    PFOp op = EFOP(e, k);
     const int kind = uni(op->kind), n_b = uni(op->n_b);
     const int a0 = uni(op->a0), a1 = uni(op->a1), b0 = uni(op->b0), b1 = uni(op->b1);
     if (kind == MOOG_FORCE_COLLISION) {
-      if (!(e.dbg & 1)) {
+      if (!(EDBG(e) & 1)) {
         PROF_T0;
         CollP cp;
         cp.symmetric = uni(op->symmetric); cp.upd = uni(op->i0); cp.maxdepth = uni(op->i1); cp.elasticity = op->p0;
@@ -2362,7 +2362,7 @@ __device__ __forceinline__ void apply_physics(Env& e) {   // (forced: see the no
     else if (P->corrective[c].kind == MOOG_CORR_MAZE) { if constexpr (DYN && MOOG_WITH_MAZE) maze_physics(e, &P->corrective[c]); }
     else tether(e, &P->corrective[c], c);
   }
-  { PROF_T0; if (!(e.dbg & 2)) integrate_all(e, 1. / K); PROF_ADD(e, 5); }
+  { PROF_T0; if (!(EDBG(e) & 2)) integrate_all(e, 1. / K); PROF_ADD(e, 5); }
 }
 
 // ---- game rules ------------------------------------------------------------------------

@@ -943,13 +943,17 @@ static KArgs make_args(moog_engine* e, const void* actions, const moog_inject_t*
   return a;
 }
 
+// A specialised kernel carries no profiling word and no section watcher (csrc/moog_kernels.h KDBG): with either set the engine
+// steps with the generic kernels, which compute the same results.
+static bool steps_specialised(const moog_engine* e) { return e->spec_launch && e->step_dbg == 0 && !e->watch; }
+
 static void launch_step(moog_engine* e, hipStream_t s, const KArgs& a) {
   // (the second six: the kernels with the action-repeat loop, for calls that take more than one env-step)
   static const moog_step_launch_fn launch[12] = {moog_launch_step_f3, moog_launch_step_f4, moog_launch_step_t3,
                                                  moog_launch_step_t4, moog_launch_step_m3, moog_launch_step_m4,
                                                  moog_launch_step_f3r, moog_launch_step_f4r, moog_launch_step_t3r,
                                                  moog_launch_step_t4r, moog_launch_step_m3r, moog_launch_step_m4r};
-  if (e->spec_launch) {
+  if (steps_specialised(e)) {
     e->spec_launch(e->n_envs, e->step_lds, s, &a);
     return;
   }
@@ -1351,7 +1355,7 @@ int moog_program_step_kernel(const moog_program_t* prog, int32_t* variant, int32
 
 int moog_engine_step_kernel(moog_engine_t* e, int32_t* specialised) {
   if (!e || !specialised) return fail(MOOG_E_INVALID, "null argument");
-  *specialised = e->spec_launch ? 1 : 0;
+  *specialised = steps_specialised(e) ? 1 : 0;
   return MOOG_OK;
 }
 

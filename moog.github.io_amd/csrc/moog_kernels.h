@@ -112,27 +112,7 @@ __device__ inline void store_record(const Env& e, const HotLayout& h, const moog
   }
 }
 
-// The (force, layer a, layer b) combinations of a program in the order physics.py:96-108 visits them.
-#include <vector>
-inline std::vector<FOp> moog_flatten_forces(const moog_program_t* p) {
-  std::vector<FOp> out;
-  for (int fi = 0; fi < p->n_forces; ++fi) {
-    const moog_force_t& F = p->forces[fi];
-    for (int a = 0; a < F.n_a; ++a) {
-      FOp op = {};
-      op.fi = fi; op.kind = F.kind; op.symmetric = F.symmetric; op.i0 = F.i0; op.i1 = F.i1; op.p0 = F.p0; op.p1 = F.p1;
-      op.a0 = p->layer_slot0[F.layers_a[a]]; op.a1 = op.a0 + p->layer_nslots[F.layers_a[a]];
-      op.n_b = F.n_b;
-      if (F.n_b == 0) { out.push_back(op); continue; }
-      for (int b = 0; b < F.n_b; ++b) {
-        op.b0 = p->layer_slot0[F.layers_b[b]]; op.b1 = op.b0 + p->layer_nslots[F.layers_b[b]];
-        out.push_back(op);
-      }
-    }
-  }
-  return out;
-}
-
+// (the flattened force list KArgs::fops points to: moog_flatten_forces, moog_fops.h)
 struct KArgs {
   const moog_program_t* P;
   moog_layout_t L;       // layout of the records in HBM (the ABI's)
@@ -151,15 +131,15 @@ struct KArgs {
   int32_t* step_type;
   int32_t mode;
   const int16_t* vslot;
-  int32_t dbg;
+  int32_t dbg;           // profiling word (moog_engine_set_debug): the generic kernels only, see KDBG
   const int32_t* perm;   // launch order (or null)
   float* cost;           // per-env cycles of this step (or null)
   int32_t* fault_flag;   // host-visible word: OR of every fault bit raised by any env (deferred fault surfacing)
   int32_t* layer_hw;     // usage of the dynamic layers (Env::layer_hw) or null
   int32_t act_f32;       // 1: `actions` holds float32 values (moog_engine_set_action_dtype)
   int32_t xstack_off;    // byte offset of the per-lane expression stacks in a wave's LDS area (Env::xstack), 0: none
-  const FOp* fops;       // flattened force list (moog_flatten_forces) and its length
-  int32_t n_fops;
+  const FOp* fops;       // flattened force list (moog_flatten_forces) and its length; a specialised kernel has the list as a
+  int32_t n_fops;        //   constant and ignores both
   int32_t* watch;        // section sampling (moog_engine_read_watch): [n_envs][MOOG_WATCH_SECTIONS] sample counts, or null
   int32_t watch_off;     // byte offset of the watcher's words in the workgroup's LDS
   // reset pool (moog_engine_set_reset_pool; the kernels that carry every component only): per env one record of the NEXT
@@ -184,6 +164,14 @@ struct KArgs {
 };
 
 enum { MODE_STEP = 0, MODE_PHYSICS = 1, MODE_RESET_MASK = 2, MODE_FILL = 3 };
+
+// The profiling word as the kernels read it: the constant 0 in a program-specialised build (its counters and early exits are
+// not compiled; the engine launches the generic kernels when a word is set, launch_step).
+#ifdef MOOG_SPEC_PROGRAM_INC
+#define KDBG(a_) 0
+#else
+#define KDBG(a_) ((a_).dbg)
+#endif
 
 extern __shared__ __attribute__((aligned(16))) unsigned char moog_lds[];
 
@@ -217,7 +205,7 @@ __device__ inline void bind_env(Env& e, const KArgs& a, int env, unsigned char* 
     e.gtele = EQ(e) + H.o_tele;
   }
   e.vslot = a.vslot;
-  e.dbg = a.dbg;
+  e.dbg = KDBG(a);
   e.n_path = 0; e.n_resp = 0; e.n_disj = 0;
   e.layer_hw = a.layer_hw;
   e.cell_tab_n = 0; e.cell_nw = 0;
@@ -249,7 +237,7 @@ struct RmSrcEnv {
 // to HBM -- colours, opacities -- is read back from there: same wavefront, stores and loads in order behind wsync).
 __device__ __forceinline__ void emit_draw_record(const Env& e, const KArgs& a, int env) {
   if (!a.draw.out) return;
-  const long long t_emit = (a.dbg & 256) ? clock64() : 0;   // (profiling aid: the emitter's cycles instead of the step type, tools/emit_cycles.py)
+  const long long t_emit = (KDBG(a) & 256) ? clock64() : 0;   // (profiling aid: the emitter's cycles instead of the step type, tools/emit_cycles.py)
   wsync();
   RmSrcEnv src;
   src.e = &e; src.vi = a.draw_vinfo;
@@ -259,8 +247,8 @@ __device__ __forceinline__ void emit_draw_record(const Env& e, const KArgs& a, i
   RmEmitScratch sc;
   rm_emit_scratch(a.draw.ncopy > 1 ? reinterpret_cast<int32_t*>(ECAND(e)) : reinterpret_cast<int32_t*>(EBB(e)), a.draw.slots, a.draw.ncopy, &sc);
   long long clk[5];
-  rm_emit(a.draw, src, env, e.lane, sc, EL(e).TOTV, (a.dbg & 256) ? clk : nullptr);
-  if ((a.dbg & 256) && e.lane == 0 && a.step_type) {   // (the emitter's cycles, and phase by phase: prefix | slots | vertex slots | items)
+  rm_emit(a.draw, src, env, e.lane, sc, EL(e).TOTV, (KDBG(a) & 256) ? clk : nullptr);
+  if ((KDBG(a) & 256) && e.lane == 0 && a.step_type) {   // (the emitter's cycles, and phase by phase: prefix | slots | vertex slots | items)
     a.step_type[env] = (int32_t)(clock64() - t_emit);
     if (a.discount) a.discount[env] = (double)(clk[1] - clk[0]) + 65536.0 * (double)(clk[2] - clk[1]);
     if (a.reward) a.reward[env] = (double)(clk[3] - clk[2]) + 65536.0 * (double)(clk[4] - clk[3]);
@@ -640,7 +628,7 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
   int32_t* gq = a.i32 + (size_t)env * a.L.i32_per_env;
   Env e;
   bind_env(e, a, env, lds, lane);
-  const long long t_begin = (a.dbg & 128) ? clock64() : 0;
+  const long long t_begin = (KDBG(a) & 128) ? clock64() : 0;
   double* gf = a.f64 + (size_t)env * a.L.f64_per_env;
   { PROF_T0; load_record(e, a.H, a.L, gf, gq); PROF_ADD(e, 9); }
   if (e.inj && e.lane == 0) EQ(e)[EL(e).o_rng + 2] = 0;
@@ -666,9 +654,9 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
       if (a.step_type) a.step_type[env] = 0;
       if (a.repeat_count) a.repeat_count[env] = 0;
 #ifdef MOOG_PROFILE   // tools/reset_profile.py: cycles of the reset and of one of its sections instead of NaN
-      if ((a.dbg & 128) && a.discount) {
+      if ((KDBG(a) & 128) && a.discount) {
         a.discount[env] = (double)(clock64() - t_begin);
-        if (a.reward) a.reward[env] = (a.dbg >> 8) ? (double)e.prof[((a.dbg >> 8) & 31) - 1] : 0.0;
+        if (a.reward) a.reward[env] = (KDBG(a) >> 8) ? (double)e.prof[((KDBG(a) >> 8) & 31) - 1] : 0.0;
       }
 #endif
     }
@@ -752,11 +740,11 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
   emit_draw_record(e, a, env);   // (before the record's stores: a wave waits once for its stores to drain, at its end)
   store_record(e, a.H, a.L, gf, gq, a.fault_flag);
   if (a.cost && e.lane == 0) a.cost[env] = moog_cost_ema((float)(clock64() - t_sched), a.cost[env]);
-  if ((a.dbg & 128) && e.lane == 0 && a.discount) {   // profiling aid: cycles and work counters instead of outputs
+  if ((KDBG(a) & 128) && e.lane == 0 && a.discount) {   // profiling aid: cycles and work counters instead of outputs
     a.discount[env] = (double)(clock64() - t_begin);
     if (a.reward) a.reward[env] = (double)(e.n_path + 100000 * e.n_resp) + 1e10 * (double)e.n_disj;
 #ifdef MOOG_PROFILE
-    if (a.reward && (a.dbg >> 8)) a.reward[env] = (double)e.prof[((a.dbg >> 8) & 31) - 1];
+    if (a.reward && (KDBG(a) >> 8)) a.reward[env] = (double)e.prof[((KDBG(a) >> 8) & 31) - 1];
 #endif
   }
 }

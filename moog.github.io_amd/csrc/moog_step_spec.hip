@@ -1,7 +1,8 @@
 // moog_step_spec.hip -- the step kernel specialised for ONE program (built by moog/_spec.py, loaded by moog_engine.hip).
 //   hipcc ... -DMOOG_SPEC_PROGRAM_INC='"<generated>.inc"' -DMOOG_STEP_DYN=0|1|2 -DMOOG_STEP_WPS=2|3|4 -shared -o step_<hash>_d<dyn>w<wps>.so
-// The generated include defines `static const moog_program_t MOOG_SPEC_PROGRAM = {...};` and MOOG_SPEC_HASH (FNV-1a 64 of
-// the program's bytes).  Same source, same arithmetic as the generic kernels (moog_step_inst.hip): results are bit-identical
+// The generated include defines `constexpr static const moog_program_t MOOG_SPEC_PROGRAM = {...};` and MOOG_SPEC_HASH (FNV-1a
+// 64 of the program's bytes); the flattened force list is a constant derived from it (moog_fops.h), and KArgs::fops / n_fops /
+// dbg are ignored.  Same source, same arithmetic as the generic kernels (moog_step_inst.hip): results are bit-identical
 // (tests/test_gpu_parity.py::test_specialised_step_kernel_is_result_neutral); only what the program never uses is gone.
 #include <hip/hip_runtime.h>
 

@@ -14,7 +14,8 @@ env.enable_cost_schedule()
 env.reset()
 for _ in range(30):
     env.step(env.random_action())
-env.set_debug(step_debug=256)
+env.set_debug(step_debug=256)   # (the engine steps with the generic kernels while a profiling word is set: the emitter is the same code)
+kernel = env.step_kernel()
 emit, total = [], []
 for _ in range(10):
     ts = env.step(env.random_action())
@@ -26,6 +27,6 @@ env.set_debug(step_debug=0)
 emit, ph = np.stack(emit), np.stack(total)
 ok = np.isfinite(ph).all(axis=1)
 print('%s, %d envs, step kernel %s: emitter cycles per env-step  mean %.0f  p50 %.0f  p99 %.0f  max %.0f' % (
-    name, n, env.step_kernel(), emit.mean(), np.percentile(emit, 50), np.percentile(emit, 99), emit.max()))
+    name, n, kernel, emit.mean(), np.percentile(emit, 50), np.percentile(emit, 99), emit.max()))
 print('   by phase (mean cycles; shader clock):  prefix check %.0f | slots: colours, liveness, scan %.0f | vertex slots: points, bounds %.0f | items: rows, records %.0f' % tuple(
     float(np.nanmean(np.where(ok, ph[:, k], np.nan))) for k in range(4)))

@@ -3,7 +3,8 @@
 The step kernel lasts as long as its slowest env, so this is the number to optimise: the pre-step records
 and actions of the heaviest envs of a few calls are captured once (`capture`), and `bench` replays exactly those steps --
 tiled over a small batch (one wavefront per CU: the env's own dependent chain) and over a full batch (3 waves per SIMD) --
-and prints their cycle counts (s_memtime at entry / exit of the wavefront, MOOG_STEP_DEBUG=128).  The work replayed is
+and prints their cycle counts (s_memtime at entry / exit of the wavefront, MOOG_STEP_DEBUG=128: the generic step kernel's --
+a specialised kernel carries no profiling word, the engine does not use it while one is set).  The work replayed is
 identical from run to run (the step path draws no random numbers on this workload), so builds can be compared to 0.1 %.
 
     python tools/heavy_bench.py capture [workload]      -> gpurun_out/heavy_<workload>.npz  (copy to tools/ubench/)
@@ -81,6 +82,7 @@ for n in ([int(os.environ['HEAVY_ONLY'])] if os.environ.get('HEAVY_ONLY') else (
             cyc.append((ts.discount.cpu().numpy().copy(), ts.reward.cpu().numpy().copy(), e0.elapsed_time(e1) * 1e3))
         out[s] = cyc[-1]
     c, r, us = out[0]
+    print('step kernel measured:', env.step_kernel())
     cnt = r % 1e10
     print('%s x %d envs (%d distinct heavy envs): cycles mean %.0f  p50 %.0f  max %.0f   call %.0f us   path tests %.1f searches %.1f' % (
         name, n, m, c.mean(), np.median(c), c.max(), us, (cnt % 100000).mean(), (cnt // 100000).mean()))

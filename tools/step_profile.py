@@ -13,7 +13,7 @@ for sel in [0, 7, 8] + [s for s, _ in SECTIONS]:
     env = environment.BatchedEnvironment(num_envs=int(os.environ.get('MOOG_PROFILE_ENVS', 4096)), seed=1, **example_configs.load(name))
     env.check_faults = False
     env.reset()
-    env.set_debug(128 | (sel << 8), 0)
+    env.set_debug(128 | (sel << 8), 0)   # (the engine steps with the generic kernels while a profiling word is set)
     for k in range(int(os.environ.get("MOOG_PROFILE_STEPS", 40))):
         ts = env.step(env.random_action())
     res[sel] = (ts.discount.cpu().numpy().copy(), ts.reward.cpu().numpy().copy())

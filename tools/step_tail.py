@@ -1,4 +1,6 @@
-"""Per-env cycle counts of the step kernel (MOOG_STEP_DEBUG=128 writes clock64 deltas into `discount`)."""
+"""Per-env cycle counts of the step kernel (MOOG_STEP_DEBUG=128 writes clock64 deltas into `discount`).
+The profiling word lives in the generic kernels only: with it set the engine steps with them even when a specialised kernel of
+the program is built (the printed kernel says so), so the counts are the generic kernel's."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'moog.github.io_amd'))
 os.environ['MOOG_STEP_DEBUG'] = '128'
@@ -11,6 +13,7 @@ STEPS = int(sys.argv[3]) if len(sys.argv) > 3 else 60
 env = environment.BatchedEnvironment(num_envs=N, seed=1, **example_configs.load(NAME))
 env.check_faults = False
 env.reset()
+print('step kernel measured:', env.step_kernel())
 for k in range(STEPS):
     ts = env.step(env.random_action())
     if k % 10 == 9:
