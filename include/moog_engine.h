@@ -51,6 +51,8 @@ extern "C" {
 #define MOOG_MAX_MORE_ACTIONS 3 /* MOOG_MAX_ACTIONS - 1 */
 #define MOOG_NUM_FACTORS 14
 #define MOOG_MAX_VIEWS 4     /* PILRenderer observers one engine draws: the program's render + 3 extra views (moog_engine_add_view) */
+#define MOOG_MAX_TABLES 4    /* SpriteTable observers one engine writes (moog_engine_add_table) */
+#define MOOG_MAX_TABLE_COLS 17 /* columns of one table: MOOG_TCOL_COUNT */
 #define MOOG_MAX_HDRAWS 32   /* draws a state_initializer takes from np.random directly (per reset) */
 #define MOOG_MAX_OP_DRAWS 24 /* draws of one generation op: its sampled factors + the direct draws made between them */
 
@@ -698,11 +700,37 @@ typedef struct {
 
 typedef struct moog_engine moog_engine_t;
 
+/* A sprite table (the SpriteTable observer): one dense [n_envs][n_rows][n_cols] tensor of per-sprite features, written on
+ * the device from the state records.  Row r shows sprite slot row_slot[r], column c the attribute cols[c] (MOOG_TCOL_*).  A
+ * live slot's row holds the record's values converted to `dtype` with one round-to-nearest-even (float64, or int32 for
+ * opacity / shape_id / n_vertices; inf and NaN pass through, float16 overflow gives inf); a dead slot's row is all zeros. */
+enum {
+  MOOG_TCOL_ALIVE = 0,   /* 1 (a dead slot's row is zero, this column included) */
+  MOOG_TCOL_X, MOOG_TCOL_Y, MOOG_TCOL_ANGLE,
+  MOOG_TCOL_SCALE,       /* needs program.sprite_factors (layout o_scale) */
+  MOOG_TCOL_C0, MOOG_TCOL_C1, MOOG_TCOL_C2, MOOG_TCOL_OPACITY,
+  MOOG_TCOL_X_VEL, MOOG_TCOL_Y_VEL, MOOG_TCOL_ANGLE_VEL, MOOG_TCOL_MASS,
+  MOOG_TCOL_ASPECT,      /* aspect_ratio; needs program.sprite_factors (layout o_aspect) */
+  MOOG_TCOL_LAYER,       /* index of the slot's layer in the state (program.slot_layer) */
+  MOOG_TCOL_SHAPE_ID,    /* the shape-table id (o_shape) */
+  MOOG_TCOL_N_VERTICES,
+  MOOG_TCOL_COUNT
+};
+enum { MOOG_TABLE_F32 = 0, MOOG_TABLE_F16 = 1 };
+typedef struct {
+  int32_t n_rows;   /* 1 .. MOOG_MAX_SLOTS */
+  int32_t n_cols;   /* 1 .. MOOG_MAX_TABLE_COLS */
+  int32_t dtype;    /* MOOG_TABLE_F32 / MOOG_TABLE_F16 */
+  int32_t cols[MOOG_MAX_TABLE_COLS];
+  int32_t row_slot[MOOG_MAX_SLOTS];
+} moog_table_t;
+
 /* kernel ids for moog_engine_kernel_time() */
+/* MOOG_K_TABLES: the one launch that writes a call's sprite tables (moog_engine_add_table). */
 /* MOOG_K_RASTER: the program's own frames (views[0]); MOOG_K_VIEWS: everything the extra views of moog_engine_add_view cost a
  * call -- their one derive launch (which also derives the primary's records when a render call needs them) and their raster,
  * crop and resize launches */
-enum { MOOG_K_STEP = 0, MOOG_K_RASTER = 1, MOOG_K_RESET = 2, MOOG_K_VIEWS = 3, MOOG_K_COUNT = 4 };
+enum { MOOG_K_STEP = 0, MOOG_K_RASTER = 1, MOOG_K_RESET = 2, MOOG_K_VIEWS = 3, MOOG_K_TABLES = 4, MOOG_K_COUNT = 5 };
 
 int moog_abi_version(void);
 /* The digest of the kernel sources and hipcc flags the library was built from (moog/_digest.py: 64 bits of SHA-256 over
@@ -769,6 +797,25 @@ int moog_engine_render(moog_engine_t* e, uint8_t* image_dev, void* hip_stream);
 int moog_engine_add_view(moog_engine_t* e, const moog_render_t* render, int32_t* view);
 int moog_engine_set_view_image(moog_engine_t* e, int32_t view, uint8_t* image_dev);
 int moog_engine_view_raster_path(moog_engine_t* e, int32_t view, int32_t* path);
+
+/* Sprite tables.  Replaces what a state-based agent assembles on the host from `RawState` (observers/raw_state.py:17-19
+ * hands out the state itself; the reference has no tensor form of it): moog_engine_add_table adds one table to the engine
+ * and returns its index (0 .. MOOG_MAX_TABLES - 1) in *table.  Like the extra views, tables belong to the engine handle,
+ * never to the program: its bytes, its hash and the step, reset and raster kernels do not know about them.
+ * MOOG_E_INVALID: a row's slot outside 0 .. n_slots - 1, an unknown column id or dtype, MOOG_TCOL_SCALE / MOOG_TCOL_ASPECT on
+ * a program without sprite_factors (o_scale == -1), n_rows / n_cols out of range, or a table beyond MOOG_MAX_TABLES.
+ * moog_engine_set_table_buffer binds the device buffer [n_envs][n_rows][n_cols] of the table's dtype the table is written
+ * to (borrowed; 4-byte aligned for float32, 2-byte for float16; NULL unbinds).
+ * moog_engine_reset and moog_engine_step write every bound table themselves, in ONE launch for all of them, on the caller's
+ * stream behind the step launch and the late-reset launch of the call: the tables show the records as the call left them
+ * (after the last env-step of an action repeat; an env the call reset shows its new episode's first state).  An engine
+ * without a bound table launches nothing and pays one comparison.  moog_engine_observe_tables is that launch on its own
+ * (Environment.observation, environment.py:128-131); it is not an error to call it with no table bound.
+ * Limits: at most MOOG_MAX_TABLES tables, MOOG_MAX_SLOTS rows and MOOG_MAX_TABLE_COLS columns each; no vertices, no
+ * derived (normalised, egocentric) columns; moog_engine_physics_only and moog_engine_render write no tables. */
+int moog_engine_add_table(moog_engine_t* e, const moog_table_t* table_desc, int32_t* table);
+int moog_engine_set_table_buffer(moog_engine_t* e, int32_t table, void* table_dev);
+int moog_engine_observe_tables(moog_engine_t* e, void* hip_stream);
 
 /* Optional launch-order schedule for the step kernel (pure performance hint, results do
  * not depend on it).  `cost_dev` (float[n_envs], borrowed; zeroed by this call) holds a moving average of every env's

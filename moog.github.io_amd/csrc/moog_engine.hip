@@ -20,6 +20,7 @@
 #include "moog_kernels.h"
 
 #include "moog_raster.h"
+#include "moog_sprite_table.h"
 #include <dlfcn.h>
 #include <unistd.h>
 
@@ -74,6 +75,13 @@ struct RView {
   uint8_t* s_bg = nullptr;
 };
 
+// A sprite table of the engine (moog_engine_add_table): the kernel's descriptor, its rows on the device, and -- in desc.out --
+// the bound buffer (moog_engine_set_table_buffer), or null.
+struct STable {
+  StTable desc{};
+  int32_t* d_rows = nullptr;
+};
+
 struct moog_engine {
   moog_program_t prog;
   moog_layout_t L;
@@ -101,6 +109,8 @@ struct moog_engine {
   uint8_t* late_mask = nullptr;   // [n_envs]
   RView views[MOOG_MAX_VIEWS];
   int n_views = 1;               // views[0] and the extra views added so far
+  STable tables[MOOG_MAX_TABLES];
+  int n_tables = 0, n_bound_tables = 0;   // tables added so far; how many of them have a buffer
   bool frameless = false;        // render 0 x 0: the program draws no frames (no raster state at all)
   uint8_t* aa_canvas = nullptr;   // shared by the anti-aliased views: [aa_chunk][canvas_h][pad_w][3] of whichever is drawn
   uint8_t* aa_tmp = nullptr;      // [aa_chunk][canvas_h][width rounded up to 4][3]
@@ -160,6 +170,7 @@ static void free_engine(moog_engine* e) {
     if (v.aa_tables) hipFree(v.aa_tables);
     if (v.rows_seen) hipHostFree(v.rows_seen);
   }
+  for (STable& t : e->tables) if (t.d_rows) hipFree(t.d_rows);
   if (e->s_f64) hipFree(e->s_f64);
   if (e->s_i32) hipFree(e->s_i32);
   if (e->aa_canvas) hipFree(e->aa_canvas);
@@ -1112,6 +1123,25 @@ static int launch_frames(moog_engine* e, uint8_t* image, hipStream_t s, bool dra
   return launch_raster(e, p, image, s, draw_ready || join);
 }
 
+// Every bound sprite table of the engine from the records as they are on stream s: one launch (moog_sprite_table.h).  An
+// engine without a bound table returns at the first comparison.
+static int launch_tables(moog_engine* e, hipStream_t s) {
+  if (e->n_bound_tables == 0) return MOOG_OK;
+  StArgs a;
+  a.f64 = e->view.f64; a.i32 = e->view.i32;
+  a.f64_per_env = e->L.f64_per_env; a.i32_per_env = e->L.i32_per_env;
+  a.n_envs = e->n_envs; a.chunk_envs = 0; a.o_flags = e->L.o_flags; a.n_tables = 0;
+  for (int k = 0; k < e->n_tables; ++k)
+    if (e->tables[k].desc.out) a.t[a.n_tables++] = e->tables[k].desc;
+  for (int k = a.n_tables; k < MOOG_MAX_TABLES; ++k) memset(&a.t[k], 0, sizeof a.t[k]);
+  {
+    Bracket br(e, MOOG_K_TABLES, s);
+    moog_sprite_table_launch(a, s);
+  }
+  HIPCHK(hipGetLastError());
+  return MOOG_OK;
+}
+
 // Reset pool: one fill launch behind the call that has just been enqueued on `s`, on the side streams in turn.  A fill
 // serves every env whose pool is empty when it STARTS (not just this call's), so of the launches that pile up on a
 // stream behind a fill that is under way (~10 ms of look-ahead per env; calls come every fraction of a millisecond) the
@@ -1175,6 +1205,7 @@ int moog_engine_reset(moog_engine_t* e, const uint8_t* env_mask_dev, const moog_
   }
   HIPCHK(hipGetLastError());
   if (e->pool_on && !(inject && inject->uniforms) && (rc = pool_kick(e, s)) != MOOG_OK) return rc;
+  if ((rc = launch_tables(e, s)) != MOOG_OK) return rc;
   if (out && out->image) return launch_frames(e, out->image, s);
   return MOOG_OK;
 }
@@ -1211,6 +1242,7 @@ int moog_engine_step(moog_engine_t* e, const void* actions_dev, const moog_injec
     HIPCHK(hipEventRecord(e->ev_sched_done, e->sched_stream));
     e->sched_pending = true;
   }
+  if ((rc = launch_tables(e, s)) != MOOG_OK) return rc;
   if (out && out->image) return launch_frames(e, out->image, s, emit);
   return MOOG_OK;
 }
@@ -1436,6 +1468,41 @@ int moog_engine_set_view_image(moog_engine_t* e, int32_t view, uint8_t* image_de
   if (view < 1 || view >= e->n_views) return fail(MOOG_E_INVALID, "no such extra view (the primary's frames are the calls' own image)");
   e->views[view].image = image_dev;
   return MOOG_OK;
+}
+
+int moog_engine_add_table(moog_engine_t* e, const moog_table_t* table_desc, int32_t* table) {
+  if (!e || !table_desc || !table) return fail(MOOG_E_INVALID, "null argument");
+  if (e->n_tables >= MOOG_MAX_TABLES) return fail(MOOG_E_INVALID, "at most MOOG_MAX_TABLES sprite tables per engine");
+  STable& t = e->tables[e->n_tables];
+  int32_t rows[MOOG_MAX_SLOTS];
+  StTable d;
+  memset(&d, 0, sizeof d);
+  const char* why = moog_st_describe(&e->prog, &e->L, table_desc, &d, rows);
+  if (why) return fail(MOOG_E_INVALID, why);
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipMalloc(&t.d_rows, sizeof(int32_t) * (size_t)table_desc->n_rows));
+  HIPCHK(hipMemcpy(t.d_rows, rows, sizeof(int32_t) * (size_t)table_desc->n_rows, hipMemcpyHostToDevice));
+  d.rows = t.d_rows;
+  t.desc = d;
+  *table = e->n_tables++;
+  return MOOG_OK;
+}
+
+int moog_engine_set_table_buffer(moog_engine_t* e, int32_t table, void* table_dev) {
+  if (!e) return fail(MOOG_E_INVALID, "null engine");
+  if (table < 0 || table >= e->n_tables) return fail(MOOG_E_INVALID, "no such sprite table");
+  StTable& d = e->tables[table].desc;
+  if ((uintptr_t)table_dev & (d.dtype == MOOG_TABLE_F16 ? 1u : 3u))
+    return fail(MOOG_E_INVALID, "sprite table buffer must be aligned to its element type");
+  e->n_bound_tables += (table_dev ? 1 : 0) - (d.out ? 1 : 0);
+  d.out = table_dev;
+  return MOOG_OK;
+}
+
+int moog_engine_observe_tables(moog_engine_t* e, void* hip_stream) {
+  const int rc = ready(e);
+  if (rc) return rc;
+  return launch_tables(e, (hipStream_t)hip_stream);
 }
 
 int moog_engine_kernel_variant(moog_engine_t* e, int32_t* variant, int32_t* late_reset) {

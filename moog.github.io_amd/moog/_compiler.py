@@ -26,9 +26,11 @@ from .state_initialization import distributions as distribs
 
 Compiled = collections.namedtuple(
     'Compiled', ['program', 'layer_names', 'layer_slots', 'observer_key', 'layout', 'shape_names', 'rule_ref_index',
-                 'pstate_slots', 'dynamic_meta', 'color_fn', 'layer_n_init', 'views'])
+                 'pstate_slots', 'dynamic_meta', 'color_fn', 'layer_n_init', 'views', 'tables', 'table_rows'])
 # views: [(observer key, moog_render_t)] of the config's PILRenderers after the first, in dict order -- the engine's extra views
-# (moog_engine_add_view); never part of the program.  observer_key: the first PILRenderer's key, or None when the config has
+# (moog_engine_add_view); never part of the program.  tables: [(observer key, moog_table_t)] of the config's SpriteTables, in dict
+# order -- the engine's sprite tables (moog_engine_add_table), never part of the program either; table_rows: {key: [(layer
+# name, index in layer)] per row}.  observer_key: the first PILRenderer's key, or None when the config has
 # none (the program's render is then 0 x 0: no frames).
 
 
@@ -1321,10 +1323,15 @@ def compile_config(state_initializer, physics, task, action_space, observers, ga
     # ---- observer -----------------------------------------------------------------------
     obs_items = list(observers.items()) if observers else []
     renderers = [(k, o) for k, o in obs_items if isinstance(o, observers_lib.PILRenderer)]
-    others = [o for _, o in obs_items if not isinstance(o, (observers_lib.PILRenderer, observers_lib.RawState))]
+    others = [o for _, o in obs_items
+              if not isinstance(o, (observers_lib.PILRenderer, observers_lib.RawState, observers_lib.SpriteTable))]
     if others:
-        raise NotImplementedError('observers other than PILRenderer and RawState are not lowered (%s)'
+        raise NotImplementedError('observers other than PILRenderer, RawState and SpriteTable are not lowered (%s)'
                                   % (', '.join(sorted(set(type(o).__name__ for o in others))),))
+    table_items = [(k, o) for k, o in obs_items if isinstance(o, observers_lib.SpriteTable)]
+    if len(table_items) > _abi.MOOG_MAX_TABLES:
+        raise NotImplementedError('at most %d SpriteTable observers per config (MOOG_MAX_TABLES), got %d'
+                                  % (_abi.MOOG_MAX_TABLES, len(table_items)))
     if len(renderers) > _abi.MOOG_MAX_VIEWS:
         raise NotImplementedError('at most %d PILRenderer observers per config (MOOG_MAX_VIEWS), got %d'
                                   % (_abi.MOOG_MAX_VIEWS, len(renderers)))
@@ -1417,7 +1424,12 @@ def compile_config(state_initializer, physics, task, action_space, observers, ga
                  [(slot_of[id(sp)], key, cell, table) for sp, key, cell, table in getattr(tr, 'dynamic_meta', [])
                   if id(sp) in slot_of],
                  # PILRenderer(color_to_rgb=<a callable>): evaluated on the host (environment.py _refresh_colors)
-                 color_fn, layer_n_init, views)
+                 color_fn, layer_n_init, views, [], {})
+    # SpriteTables read the finished layout (rows = the slots of their layers) and leave the program alone
+    for key, o in table_items:
+        T, rows = o.lower(P, layer_names)
+        c.tables.append((key, T))
+        c.table_rows[key] = rows
     # shape id -> Sprite.shape value (sprite.py:517-523): the name, or 'custom' for raw vertices
     c.shape_names.extend(k[1] if k[0] == 'name' else 'custom' for k, _ in shapes.entries)
     return c

@@ -6,7 +6,8 @@
 float64[N] (NaN where the reference returns None), discount float64[N],
 observation {'image': uint8[N,H,W,3]} -- all torch tensors on the device; a config with several
 PILRenderers gets one such tensor per renderer key (the engine's extra views), one with none only
-its RawState entries.
+its RawState entries; a SpriteTable observer's entry is its float32 / float16 tensor [N, rows, columns], rewritten in place
+like the frames.
 Auto-reset follows environment.py:100-101 per env: the call after a LAST
 timestep ignores that env's action and returns a FIRST timestep.
 
@@ -112,12 +113,14 @@ class BatchedEnvironment(object):
             (self.state_f64, self.state_i32, self.reward, self.discount, self.step_type, self.image) = _buffers[:6]
             self.view_images = _buffers[6] if len(_buffers) > 6 else None
             self.repeat_count = _buffers[7] if len(_buffers) > 7 else None
+            self.tables = _buffers[8] if len(_buffers) > 8 else None
         else:
             with torch.cuda.device(self.device):
                 (self.state_f64, self.state_i32, self.reward, self.discount, self.step_type,
                  self.image) = self.allocate_buffers(torch, L, P, n, self.device)
             self.view_images = None
             self.repeat_count = None
+            self.tables = None
         if self.repeat_count is None:
             # env-steps each env took in the last step() call: action_repeat, fewer where the episode ended inside the call,
             # 0 where the call reset the env (a FIRST timestep) and after reset()
@@ -125,6 +128,9 @@ class BatchedEnvironment(object):
         if self.view_images is None:
             with torch.cuda.device(self.device):
                 self.view_images = self.allocate_view_buffers(torch, self.compiled, n, self.device)
+        if self.tables is None:
+            with torch.cuda.device(self.device):
+                self.tables = self.allocate_table_buffers(torch, self.compiled, n, self.device)
         # frames per PILRenderer key, in the config's order: the primary's `image` and the extra views' tensors
         self._frames = {}
         if self.compiled.observer_key is not None:
@@ -144,6 +150,7 @@ class BatchedEnvironment(object):
         view.i32 = ctypes.cast(self.state_i32.data_ptr(), ctypes.POINTER(ctypes.c_int32))
         _engine.check(self._lib, self._lib.moog_engine_load_state(self._handle, ctypes.byref(view)))
         self._attach_views()
+        self._attach_tables()
         self._out = _abi.StepOut()
         self._out.reward = ctypes.cast(self.reward.data_ptr(), ctypes.POINTER(ctypes.c_double))
         self._out.discount = ctypes.cast(self.discount.data_ptr(), ctypes.POINTER(ctypes.c_double))
@@ -213,6 +220,40 @@ class BatchedEnvironment(object):
             _engine.check(self._lib, self._lib.moog_engine_set_view_image(
                 self._handle, idx.value, ctypes.c_void_p(self.view_images[key].data_ptr())))
             self._view_index[key] = idx.value
+
+    def _attach_tables(self):
+        """The config's SpriteTables: a sprite table of the engine each (moog_engine_add_table), written into its own tensor
+        by every reset / step call and by observation()."""
+        self._table_index = {}
+        for key, table in self.compiled.tables:
+            idx = ctypes.c_int32()
+            with self._torch.cuda.device(self.device):
+                _engine.check(self._lib, self._lib.moog_engine_add_table(self._handle, ctypes.byref(table), ctypes.byref(idx)))
+            _engine.check(self._lib, self._lib.moog_engine_set_table_buffer(
+                self._handle, idx.value, ctypes.c_void_p(self.tables[key].data_ptr())))
+            self._table_index[key] = idx.value
+
+    def _observe_tables(self):
+        if self.compiled.tables:
+            with self._torch.cuda.device(self.device):
+                _engine.check(self._lib, self._lib.moog_engine_observe_tables(self._handle, self._stream()))
+
+    @staticmethod
+    def allocate_table_buffers(torch, compiled, n, device):
+        """{key: float32 / float16 [n, rows, columns]} for the config's SpriteTables."""
+        return {key: torch.zeros((n, int(T.n_rows), int(T.n_cols)), device=device,
+                                 dtype=torch.float16 if T.dtype == _abi.MOOG_TABLE_F16 else torch.float32)
+                for key, T in compiled.tables}
+
+    def table_rows(self, key):
+        """[(layer name, index in layer)] for every row of the SpriteTable observer `key`."""
+        return list(self.compiled.table_rows[key])
+
+    def table_columns(self, key):
+        """The column names of the SpriteTable observer `key`."""
+        if key not in self.compiled.table_rows:
+            raise KeyError('%r is not a SpriteTable observer of this config' % (key,))
+        return tuple(self.observers[key].columns)
 
     @staticmethod
     def allocate_view_buffers(torch, compiled, n, device):
@@ -422,6 +463,8 @@ class BatchedEnvironment(object):
         for key, o in self.observers.items():   # the reference's dict order
             if isinstance(o, raw_state.RawState):
                 obs[key] = raw_state.StateView(self)
+            elif key in self.tables:
+                obs[key] = self.tables[key]
             else:
                 obs[key] = self._frames[key]
         return obs
@@ -584,6 +627,10 @@ class BatchedEnvironment(object):
             view.i32 = ctypes.cast(self.state_i32.data_ptr(), ctypes.POINTER(ctypes.c_int32))
             _engine.check(self._lib, self._lib.moog_engine_load_state(self._handle, ctypes.byref(view)))
             self._attach_views()
+            # (other capacities, other row counts: new tensors, filled from the records that have just moved over)
+            self.tables = self.allocate_table_buffers(torch, new_c, self.num_envs, self.device)
+            self._attach_tables()
+            self._observe_tables()
             if f32:
                 _engine.check(self._lib, self._lib.moog_engine_set_action_dtype(self._handle, 1))
             self._apply_action_repeat()
@@ -780,6 +827,7 @@ class BatchedEnvironment(object):
     def observation(self):
         """Renders the current state (environment.py:128-131)."""
         self._poll_faults()
+        self._observe_tables()
         if self._color_fn is not None:
             self._render_with_colors()
             return self._observation()
@@ -791,9 +839,10 @@ class BatchedEnvironment(object):
         return self._observation()
 
     def observation_spec(self):
-        from .observers import raw_state
-        return {k: o.observation_spec() for k, o in self.observers.items()
-                if not isinstance(o, raw_state.RawState)}
+        from .observers import raw_state, sprite_table
+        tables = dict(self.compiled.tables)   # (a SpriteTable's shape follows from this environment's layer capacities)
+        return {k: sprite_table.table_spec(tables[k]) if k in tables else o.observation_spec()
+                for k, o in self.observers.items() if not isinstance(o, raw_state.RawState)}
 
     def action_spec(self):
         return self.action_space.action_spec()
@@ -984,6 +1033,7 @@ class SubBatchedEnvironment(object):
             bufs = BatchedEnvironment.allocate_buffers(torch, L, P, self.num_envs, self.device)
             self._streams = [torch.cuda.Stream(device=self.device) for _ in range(G)]
             self.view_images = BatchedEnvironment.allocate_view_buffers(torch, self.compiled, self.num_envs, self.device)
+            self.tables = BatchedEnvironment.allocate_table_buffers(torch, self.compiled, self.num_envs, self.device)
         (self.state_f64, self.state_i32, self.reward, self.discount, self.step_type, self.image) = bufs
         with torch.cuda.device(self.device):   # (BatchedEnvironment.repeat_count, whole batch: every part writes its slice)
             self.repeat_count = torch.zeros((self.num_envs,), dtype=torch.int32, device=self.device)
@@ -992,7 +1042,8 @@ class SubBatchedEnvironment(object):
         self.parts = []
         for g in range(G):
             views = tuple(b[g * m:(g + 1) * m] for b in bufs) + (
-                {k: t[g * m:(g + 1) * m] for k, t in self.view_images.items()}, self.repeat_count[g * m:(g + 1) * m])
+                {k: t[g * m:(g + 1) * m] for k, t in self.view_images.items()}, self.repeat_count[g * m:(g + 1) * m],
+                {k: t[g * m:(g + 1) * m] for k, t in self.tables.items()})
             self.parts.append(BatchedEnvironment(
                 state_initializer, physics, task, action_space, observers, game_rules, None,
                 num_envs=m, device=self.device, seed=seed, env_index0=int(env_index0) + g * m,
@@ -1066,6 +1117,8 @@ class SubBatchedEnvironment(object):
                 obs[key] = raw_state.StateView(self)
             elif key == self.compiled.observer_key:
                 obs[key] = self.image
+            elif key in self.tables:
+                obs[key] = self.tables[key]
             else:
                 obs[key] = self.view_images[key]
         return dm_env.TimeStep(self.step_type, self.reward, self.discount, obs)
@@ -1116,6 +1169,12 @@ class SubBatchedEnvironment(object):
 
     def field(self, name):
         return BatchedEnvironment.field(self, name)
+
+    def table_rows(self, key):
+        return self.parts[0].table_rows(key)
+
+    def table_columns(self, key):
+        return self.parts[0].table_columns(key)
 
     def sprites(self, env=0):
         return BatchedEnvironment.sprites(self, env)
