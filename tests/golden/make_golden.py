@@ -15,6 +15,26 @@ writes neutral .npz fixtures (no layout of this repo is baked in):
   collisions_kat.npz     outcome of the reference's known-answer scenarios
                          (tests/moog/physics/test_collisions.py:101-293) as
                          computed by the reference itself
+  collision_pairs.npz    1211 single pairs of sprites (layers a and b of a reference Physics with one Collision
+                         force), each stepped once by the reference's own Physics.step: the before-record of
+                         both sprites in snapshot()'s vocabulary, the after-values of pos / vel / angle / angvel
+                         and of the two dtype flags, the parameter group (`groups`: elasticity, symmetric,
+                         update_angle_vel, updates_per_env_step, max_recursion_depth; twelve rows) and class
+                         bits (`cls`, names in `classes`) noted by wrapping the reference's functions while it
+                         ran (_PairProbe).  Only well-conditioned pairs are kept (a second run with every
+                         before-value moved by a relative 1e-12 must land within 1e-10 with the same class
+                         bits): 38 of 1249 candidates (3.0 %) were dropped.
+                         max_recursion_depth is 0 (the constructor's default) in six groups and 2 in six: at 0
+                         Collision.step never re-steps, so class 3 (the re-step of a top-level call resolves a
+                         further contact) occurs in the other six only.  Class 8 (Collision.step entered beyond
+                         max_recursion_depth) occurs on 389 pairs without being steered to: at a limit of 0
+                         every resolved contact ends there.
+                         An infinite mass (sprite 1) gives numbers only where the collision is neither
+                         symmetric nor rotating; elsewhere the reference divides inf by inf.  It is drawn with
+                         a chance of 0.3 in the former groups and 0.03 in the others; the 12 pairs that end
+                         in NaN are recorded as they are and count towards no coverage condition.
+                         `python tests/golden/make_golden.py collision_pairs` makes this file alone, byte for
+                         byte the same on every run.
 
 Randomness: the reference draws from numpy's global MT19937.  To
 make runs reproducible by an engine with a different generator, np.random.uniform
@@ -752,6 +772,341 @@ def make_collision_kat():
     print('collisions_kat: %d scenarios' % len(rows))
 
 
+# ---- collision pairs ----------------------------------------------------------------
+# class bits of collision_pairs.npz (`cls`), obtained by wrapping the reference's functions while it steps a pair
+PAIR_CLASSES = ('no_overlap', 'future_contact', 'one_contact', 'second_contact', 'vertex_of_0', 'vertex_of_1',
+                'disjoint_moved', 'disjoint_noop', 'depth_limit', 'circle_circle', 'circle_polygon', 'concave',
+                'infinite_mass', 'spinning', 'float32')
+PAIR_AFTER = ('pos', 'vel', 'angle', 'angvel')
+
+
+def pair_groups():
+    """The twelve parameter groups: rows of (elasticity, symmetric, update_angle_vel, updates_per_env_step,
+    max_recursion_depth).  Every value of every parameter meets u = 1 and u = 5 and both recursion limits (0, the
+    constructor's default, where Collision.step never re-steps, and 2, falling_balls' value)."""
+    rows = []
+    for e, el in enumerate((0., 0.5, 1.)):
+        for s in (0, 1):
+            for a in (0, 1):
+                rows.append((el, s, a, 5 if (e + s + a) % 2 else 1, 2 if (e + s) % 2 else 0))
+    return np.array(rows, dtype=np.float64)
+
+
+class _PairProbe(object):
+    """Wraps Collision.step, _get_collision_vectors, _directed_collision_vectors, _make_disjoint and
+    _position_correction of the reference (only while a pair is stepped) and notes which branches were taken.
+    Contacts are counted per top-level call of Collision.step (recursion_depth 0; Physics.step makes one per sub-step): one
+    resolved contact in such a call is class 2, a further one resolved by its re-step (recursion_depth >= 1) class 3.
+    Once a sprite holds a non-finite value (an infinite mass in a symmetric or rotating collision makes the reference
+    divide inf by inf) searches and _make_disjoint calls are no longer classified: what they do then says nothing
+    about the branch."""
+
+    def __init__(self):
+        self.bits = 0
+        self.searches = 0
+        self.in_call = 0      # contacts resolved so far in the current top-level call
+        self._directed = []
+        self._corrections = None
+
+    @staticmethod
+    def _finite(*sprites):
+        return all(np.all(np.isfinite(s.position)) and np.all(np.isfinite(np.asarray(s.velocity, dtype=float)))
+                   and np.isfinite(float(s.angle_vel)) and np.all(np.isfinite(s.vertices)) for s in sprites)
+
+    def _close_call(self):
+        if self.in_call == 1:
+            self.bits |= 1 << 2
+        if self.in_call >= 2:
+            self.bits |= 1 << 3
+        self.in_call = 0
+
+    def __enter__(self):
+        C, M = ref_collisions.Collision, ref_collisions
+        self._saved = (C.step, C._make_disjoint, M._get_collision_vectors, M._directed_collision_vectors,
+                       M._position_correction)
+        step, disjoint, search, directed, correction = self._saved
+        probe = self
+
+        def step_(self_, sprite_0, sprite_1, updates_per_env_step, recursion_depth=0):
+            if recursion_depth == 0:
+                probe._close_call()
+            if recursion_depth > self_._max_recursion_depth:
+                probe.bits |= 1 << 8
+            return step(self_, sprite_0, sprite_1, updates_per_env_step, recursion_depth=recursion_depth)
+
+        def directed_(*args):
+            out = directed(*args)
+            probe._directed.append(out[0])
+            return out
+
+        def search_(sprite_0, sprite_1, delta_t):
+            probe._directed = []
+            finite = probe._finite(sprite_0, sprite_1)
+            out = search(sprite_0, sprite_1, delta_t)
+            probe.searches += 1
+            point, normal = out[0], out[1]
+            if point is not None and finite:   # (the first directed search looks for sprite 1's vertices inside sprite 0)
+                probe.bits |= 1 << (5 if point is probe._directed[0] else 4)
+                if np.isscalar(normal) and np.isnan(normal):
+                    probe.bits |= 1 << 1
+                else:
+                    probe.in_call += 1
+            return out
+
+        def correction_(*args):
+            out = correction(*args)
+            probe._corrections.append(out)
+            return out
+
+        def disjoint_(self_, sprite_0, sprite_1):
+            finite = probe._finite(sprite_0, sprite_1)
+            before = np.concatenate([sprite_0.position, sprite_1.position])
+            probe._corrections = []
+            out = disjoint(self_, sprite_0, sprite_1)
+            after = np.concatenate([sprite_0.position, sprite_1.position])
+            if finite:
+                if not np.array_equal(before, after):
+                    probe.bits |= 1 << 6
+                if out or not np.all(np.isfinite(probe._corrections[0])):
+                    probe.bits |= 1 << 7
+            return out
+
+        C.step, C._make_disjoint = step_, disjoint_
+        M._get_collision_vectors, M._directed_collision_vectors, M._position_correction = search_, directed_, correction_
+        return self
+
+    def __exit__(self, *exc):
+        C, M = ref_collisions.Collision, ref_collisions
+        (C.step, C._make_disjoint, M._get_collision_vectors, M._directed_collision_vectors,
+         M._position_correction) = self._saved
+        self._close_call()
+        if self.searches == 0:
+            self.bits |= 1 << 0
+
+
+def _build_pair(spec, wiggle=None):
+    """The two reference Sprites of a pair description; `wiggle` (a RandomState): every before-value is multiplied by
+    1 +- 1e-12 afterwards."""
+    out = []
+    for d in spec:
+        s = ref_sprite.Sprite(x=0.5, y=0.5, shape=d['shape'], angle=d['angle'], scale=d['scale'],
+                              aspect_ratio=d['aspect'], mass=d['mass'])
+        s.position = np.array(d['pos'])
+        dtype = np.float32 if d['f32'] else np.float64
+        s.velocity = np.array(d['vel'], dtype=dtype)
+        # (a float32 angle_vel is a 0-d array, as distributions.Continuous hands it to every config: `+=` keeps its dtype)
+        s.angle_vel = np.asarray(d['angvel'], dtype=np.float32) if d['f32'] else float(d['angvel'])
+        if wiggle is not None:
+            w = lambda shape=None: 1. + 1e-12 * (2. * wiggle.randint(2, size=shape) - 1.)
+            v = s._path.vertices.copy()
+            v[:-1] *= w(v[:-1].shape)
+            v[-1] = v[0]
+            s._path = mpl_path.Path(v)
+            s._position = s._position * w(2)
+            s._angle = float(s._angle * w())
+            s._velocity = (s._velocity * w(2)).astype(dtype)
+            s._angle_vel = np.asarray(s._angle_vel * w(), dtype=np.float32) if d['f32'] else float(s._angle_vel * w())
+            s._mass = float(s._mass * w())
+            s._x_y_rotational_inertia = s._x_y_rotational_inertia * w(2)
+            s._max_radius = float(s._max_radius * w())
+        out.append(s)
+    return out
+
+
+def _pair_record(sprites):
+    d = {}
+    for k, s in enumerate(sprites):
+        v = np.full((VMAX, 2), np.nan)
+        v[:len(s.vertices)] = s.vertices
+        d[k] = dict(pos=np.array(s.position, dtype=np.float64), vel=np.array(s.velocity, dtype=np.float64),
+                    angle=float(s.angle), angvel=float(s.angle_vel), mass=float(s.mass), nverts=len(s.vertices), verts=v,
+                    inertia=np.array(s._x_y_rotational_inertia, dtype=np.float64), maxr=float(s.max_radius),
+                    sym_circle=bool(s.is_symmetric_circle), vel_f32=np.asarray(s.velocity).dtype == np.float32,
+                    angvel_f32=getattr(s.angle_vel, 'dtype', None) == np.float32)
+    return {key: np.stack([np.asarray(d[k][key]) for k in (0, 1)]) for key in d[0]}
+
+
+def _step_pair(sprites, group):
+    """One Physics.step of the reference on {'a': [sprite 0], 'b': [sprite 1]}: (after record, class bits of the run)."""
+    import collections
+    from moog import physics as ref_physics
+    el, sym, upd, u, depth = group
+    force = ref_collisions.Collision(elasticity=float(el), symmetric=bool(sym), update_angle_vel=bool(upd),
+                                     max_recursion_depth=int(depth))
+    phys = ref_physics.Physics((force, 'a', 'b'), updates_per_env_step=int(u))
+    state = collections.OrderedDict([('a', [sprites[0]]), ('b', [sprites[1]])])
+    with _PairProbe() as probe, np.errstate(all='ignore'):
+        phys.step(state)
+    return _pair_record(sprites), probe.bits
+
+
+def _is_concave(v):
+    e = np.roll(v, -1, axis=0) - v
+    c = e[:, 0] * np.roll(e, -1, axis=0)[:, 1] - e[:, 1] * np.roll(e, -1, axis=0)[:, 0]
+    return bool(np.any(c > 1e-12) and np.any(c < -1e-12))
+
+
+def _sample_pair(rs, pool, f32, p_inf=0.25, corner=False):
+    """A pair description steered towards contact (see make_collision_pairs).  p_inf: the chance that sprite 1's mass is
+    infinite; corner: only the corner-to-corner placement, mostly without any motion (a sprite put there by a Grid action):
+    what reaches _make_disjoint."""
+    spec = []
+    for k in (0, 1):
+        shape = pool[rs.randint(len(pool))]
+        if rs.uniform() < 0.25:
+            shape = 'circle'
+        spec.append(dict(
+            shape=shape, angle=rs.uniform(0, 2 * np.pi), scale=rs.uniform(0.03, 0.25),
+            aspect=1. if rs.uniform() < 0.3 else rs.uniform(0.6, 1.4),
+            mass=np.inf if k == 1 and rs.uniform() < p_inf else [0.5, 1., 2.][rs.randint(3)],
+            angvel=0. if rs.uniform() < 0.5 else rs.uniform(-0.3, 0.3), f32=f32,
+            pos=rs.uniform(0.3, 0.7, size=2), vel=np.zeros(2)))
+    a, b = _build_pair(spec)
+    reach = a.max_radius + b.max_radius
+    d = rs.normal(size=2)
+    d /= np.linalg.norm(d)
+    kind = 7 if corner else rs.randint(8)
+    if kind == 0:      # bounding circles apart
+        spec[1]['pos'] = spec[0]['pos'] + d * reach * rs.uniform(1.02, 1.4)
+    elif kind <= 2:    # near-touching
+        spec[1]['pos'] = spec[0]['pos'] + d * reach * rs.uniform(0.3, 1.0)
+    elif kind <= 5:    # a vertex of one just inside an edge of the other
+        p, q = (a, b) if rs.randint(2) else (b, a)
+        vq = q.vertices
+        j = rs.randint(len(vq))
+        e0, e1 = vq[j], vq[(j + 1) % len(vq)]
+        on_edge = e0 + rs.uniform(0.1, 0.9) * (e1 - e0)
+        inward = np.array([-(e1 - e0)[1], (e1 - e0)[0]])
+        inward /= np.linalg.norm(inward)
+        # the vertex of p that points most against the edge's inward direction is the one that enters first
+        i = int(np.argmin((p.vertices - p.position) @ inward))
+        shift = on_edge + inward * rs.uniform(0.0005, 0.012) - p.vertices[i]
+        if p is a:
+            spec[0]['pos'] = spec[0]['pos'] + shift
+        else:
+            spec[1]['pos'] = spec[1]['pos'] + shift
+        d = (spec[1]['pos'] - spec[0]['pos']) / np.linalg.norm(spec[1]['pos'] - spec[0]['pos'])
+    else:              # corner to corner: the outlines cross, neither holds a vertex of the other (_make_disjoint)
+        for _ in range(300):
+            d = rs.normal(size=2)
+            d /= np.linalg.norm(d)
+            b.position = a.position + d * reach * rs.uniform(0.1, 1.0)
+            if (a.overlaps_sprite(b) and not np.any(b.contains_points(a.vertices))
+                    and not np.any(a.contains_points(b.vertices))):
+                break
+        spec[1]['pos'] = np.array(b.position)
+    # velocities: about half approaching, a share receding, a share with no relative velocity (a sprite put inside another)
+    common = rs.uniform(-0.02, 0.02, size=2) if rs.uniform() < 0.5 else np.zeros(2)
+    how = 1. if corner and rs.uniform() < 0.7 else rs.uniform()
+    if how < 0.55:
+        rel = d * rs.uniform(0.005, 0.05) + rs.normal(size=2) * 0.004
+    elif how < 0.8:
+        rel = -d * rs.uniform(0.005, 0.05) + rs.normal(size=2) * 0.004
+    else:
+        rel = np.zeros(2)
+    share = 1. if not np.isfinite(spec[1]['mass']) and rs.uniform() < 0.7 else rs.uniform(0.3, 1.)
+    if corner and how == 1.:
+        spec[0]['angvel'] = spec[1]['angvel'] = 0.
+    for k, v in ((0, common + share * rel), (1, common - (1. - share) * rel)):
+        n = np.linalg.norm(v)
+        spec[k]['vel'] = v * min(1., 0.05 / n) if n > 0 else v
+    return spec
+
+
+def make_collision_pairs(per_group=85, seed=17):
+    """collision_pairs.npz: single pairs of sprites, each stepped once by the reference's own Physics.step under a
+    Collision force, with the branches the reference took (class bits) and the outcome.
+
+    Only well-conditioned pairs are kept: every candidate is stepped a second time with each before-value multiplied by
+    1 +- 1e-12; it is dropped when an after-value moves by more than 1e-10 or the class bits differ."""
+    from moog import shapes as ref_shapes
+    rs = np.random.RandomState(seed)
+    wiggle = np.random.RandomState(seed + 1)
+    pool = list(ref_shapes.SHAPES.keys()) + [
+        1.8 * np.array([[-0.3, -0.3], [0.1, -0.7], [0.4, 0.6], [-0.1, 0.25]]),
+        1.5 * np.array([[-0.5, -0.3], [-0.1, -0.7], [0.7, 0.1], [0., -0.1], [-0.3, 0.25]])]
+    groups = pair_groups()
+    G = len(groups)
+    kept = [[] for _ in range(G)]
+    tried = dropped = 0
+
+    def candidate(g, corner=False):
+        nonlocal tried, dropped
+        f32 = len(kept[g]) % 8 == 0
+        # an infinite mass gives numbers only where the collision is neither symmetric nor rotating (where every config
+        # has its walls); elsewhere the reference returns NaN for it, which a few pairs record and no more
+        p_inf = 0.3 if not groups[g][1] and not groups[g][2] else 0.03
+        spec = _sample_pair(rs, pool, f32, p_inf=p_inf, corner=corner)
+        sprites = _build_pair(spec)
+        before = _pair_record(sprites)
+        after, bits = _step_pair(sprites, groups[g])
+        after2, bits2 = _step_pair(_build_pair(spec, wiggle), groups[g])
+        tried += 1
+        for key in PAIR_AFTER:
+            x, y = after[key], after2[key]
+            same = (np.isnan(x) & np.isnan(y)) | (np.abs(x - y) <= 1e-10)
+            if not np.all(same):
+                bits2 = -1
+        if bits2 != bits or not np.array_equal(after['vel_f32'], after2['vel_f32']) \
+                or not np.array_equal(after['angvel_f32'], after2['angvel_f32']):
+            dropped += 1
+            return
+        names = [d['shape'] if isinstance(d['shape'], str) else 'custom' for d in spec]
+        circles = sum(n == 'circle' for n in names)
+        bits |= (circles == 2) << 9 | (circles == 1) << 10
+        bits |= any(_is_concave(sprites_v) for sprites_v in
+                    (before['verts'][k][:before['nverts'][k]] for k in (0, 1))) << 11
+        bits |= bool(np.isinf(before['mass']).any()) << 12 | bool((before['angvel'] != 0).any()) << 13 | bool(f32) << 14
+        kept[g].append((before, after, bits))
+
+    finite = lambda after: all(np.all(np.isfinite(after[key])) for key in PAIR_AFTER)
+
+    def counts():   # coverage counts only pairs whose recorded outcome is finite: the others are held by 'NaN stays NaN'
+        c = np.zeros(len(PAIR_CLASSES), int)
+        for rows in kept:
+            for _, after, bits in rows:
+                if finite(after):
+                    c += [(bits >> k) & 1 for k in range(len(PAIR_CLASSES))]
+        return c
+
+    contacts = lambda g: sum(1 for _, after, bits in kept[g] if bits & 0b1100 and finite(after))
+    for g in range(G):
+        while len(kept[g]) < per_group or contacts(g) < 20:
+            candidate(g)
+    must = [k for k in range(len(PAIR_CLASSES)) if k != 8]
+    deep = [g for g in range(G) if groups[g][4] > 0]
+    turn = 0
+    while counts()[must].min() < 30 and tried < 40 * per_group * G:
+        lacking = [k for k in must if counts()[k] < 30]
+        turn += 1
+        if lacking[0] == 3:        # the re-step needs a recursion limit above 0
+            candidate(deep[turn % len(deep)])
+        else:                      # (_make_disjoint is reached from corner-to-corner placements)
+            candidate(turn % G, corner=any(k in (6, 7) for k in lacking))
+    c = counts()
+    assert c[must].min() >= 30, dict(zip(PAIR_CLASSES, c))
+    rows = [(g, r) for g in range(G) for r in kept[g]]
+    out = {'groups': groups, 'group_columns': np.array(['elasticity', 'symmetric', 'update_angle_vel',
+                                                        'updates_per_env_step', 'max_recursion_depth']),
+           'classes': np.array(PAIR_CLASSES), 'group': np.array([g for g, _ in rows], np.int32),
+           'cls': np.array([r[2] for _, r in rows], np.int32), 'alive': np.ones((len(rows), 2), np.uint8)}
+    for key in rows[0][1][0]:
+        out[key] = np.stack([r[0][key] for _, r in rows])
+    for key in PAIR_AFTER + ('vel_f32', 'angvel_f32'):
+        out['after_' + key] = np.stack([r[1][key] for _, r in rows])
+    for key in ('nverts',):
+        out[key] = out[key].astype(np.int32)
+    for key in ('sym_circle', 'vel_f32', 'angvel_f32', 'after_vel_f32', 'after_angvel_f32'):
+        out[key] = out[key].astype(np.uint8)
+    path = os.path.join(HERE, 'collision_pairs.npz')
+    np.savez_compressed(path, **out)
+    print('collision_pairs: %d pairs kept of %d candidates (%d dropped as ill-conditioned, %.1f %%)  %.0f KB' % (
+        len(rows), tried, dropped, 100. * dropped / tried, os.path.getsize(path) / 1024.))
+    print('  per group:', [len(k) for k in kept], ' with a resolved contact:', [contacts(g) for g in range(G)])
+    print('  classes (pairs with a finite outcome):', {k: int(v) for k, v in zip(PAIR_CLASSES, c)})
+    print('  pairs with a NaN in the outcome: %d' % sum(not finite(r[1]) for _, r in rows))
+
+
 def make_logger_fixture():
     """A run of the reference's LoggingEnvironment (env_wrappers/logger.py) on a config without
     randomness (tether_zoo level 0): the episode files it writes, as one JSON fixture."""
@@ -794,9 +1149,13 @@ def main():
     if only == ['resize']:
         make_resize()
         return
+    if only == ['collision_pairs']:
+        make_collision_pairs()
+        return
     if not only:
         make_resize()
         make_collision_kat()   # before np.random is patched (uses no randomness anyway)
+        make_collision_pairs()
         make_predicates()
         make_raster()
     patch_numpy_random()

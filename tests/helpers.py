@@ -187,6 +187,115 @@ def fixture(name, seed=0):
         return {k: z[k] for k in z.files}
 
 
+@functools.lru_cache(maxsize=None)
+def collision_pairs():
+    """tests/golden/collision_pairs.npz (make_golden.py make_collision_pairs): single pairs stepped once by the reference,
+    with the branches it took.  Read only."""
+    with np.load(os.path.join(GOLDEN, 'collision_pairs.npz')) as z:
+        fx = {k: z[k] for k in z.files}
+    for v in fx.values():
+        v.setflags(write=False)
+    return fx
+
+
+def pair_rows(group):
+    return np.flatnonzero(collision_pairs()['group'] == group)
+
+
+def pair_config(group):
+    """The drop-in config of a parameter group of the pair corpus: one placeholder sprite in each of the layers a and b (a
+    30-vertex shape, so that every pair of the corpus fits the slots), the group's one Collision force between them."""
+    import collections
+    from moog import action_spaces, observers, physics as physics_lib, sprite, tasks
+    el, sym, upd, u, depth = collision_pairs()['groups'][group]
+    # shapes.SHAPES['circle'] is the 30-sided polygon: slot_vcap becomes 30, the corpus's VMAX (plant_pairs asserts the fit)
+    s0 = sprite.Sprite(x=0.3, y=0.3, scale=0.1, shape='circle', c0=255)
+    s1 = sprite.Sprite(x=0.7, y=0.7, scale=0.1, shape='circle', c1=255)
+    f = physics_lib.Collision(elasticity=float(el), symmetric=bool(sym), update_angle_vel=bool(upd),
+                              max_recursion_depth=int(depth))
+    return dict(
+        state_initializer=lambda: collections.OrderedDict([('a', [s0]), ('b', [s1]), ('agent', [])]),
+        physics=physics_lib.Physics((f, 'a', 'b'), updates_per_env_step=int(u)),
+        task=tasks.CompositeTask(),
+        action_space=action_spaces.Grid(action_layers='agent'),
+        observers={'image': observers.PILRenderer(image_size=(64, 64))})
+
+
+def plant_pairs(c, f64, i32, before, rows):
+    """Writes the before-records of pairs `rows` of the pair corpus `before` into the state records of a compiled
+    pair_config program, pair rows[i] into env i: every field the step reads for a live sprite (records_from_fixture is the
+    model).  Whatever else a reset left in the records (colours, opacity, counters) stays."""
+    P, L = c.program, c.layout
+    assert L.S == 2 and len(rows) <= len(f64)
+    for env, r in enumerate(rows):
+        f, q = f64[env], i32[env]
+        for s in (0, 1):
+            nv = int(before['nverts'][r, s])
+            assert before['alive'][r, s] and nv <= P.slot_vcap[s]
+            f[L.o_pos + 2 * s:L.o_pos + 2 * s + 2] = before['pos'][r, s]
+            f[L.o_vel + 2 * s:L.o_vel + 2 * s + 2] = before['vel'][r, s]
+            f[L.o_angle + s] = before['angle'][r, s]
+            f[L.o_angvel + s] = before['angvel'][r, s]
+            f[L.o_mass + s] = before['mass'][r, s]
+            f[L.o_inertia + 2 * s:L.o_inertia + 2 * s + 2] = before['inertia'][r, s]
+            f[L.o_maxr + s] = before['maxr'][r, s]
+            o = L.o_verts + 2 * P.slot_voff[s]
+            f[o:o + 2 * P.slot_vcap[s]] = 0
+            f[o:o + 2 * nv] = before['verts'][r, s, :nv].ravel()
+            fl = _abi.MOOG_F_ALIVE
+            if before['sym_circle'][r, s]:
+                fl |= _abi.MOOG_F_SYM_CIRCLE
+            if before['vel_f32'][r, s]:
+                fl |= _abi.MOOG_F_VEL_F32
+            if before['angvel_f32'][r, s]:
+                fl |= _abi.MOOG_F_ANGVEL_F32
+            q[L.o_flags + s] = fl
+            q[L.o_nverts + s] = nv
+    return f64, i32
+
+
+def pair_errors(c, f64, i32, fx, rows):
+    """Compares pos / vel / angle / angvel of both sprites of env i with the recorded after-values of pair rows[i]:
+    (worst |got - recorded| per pair [len(rows)], flags_ok [len(rows)]).  A NaN the reference produced (a symmetric or
+    rotating collision with an infinite mass divides inf by inf) must be a NaN, anything else counts as an infinite error."""
+    L = c.layout
+    n = len(rows)
+    f, q = f64[:n], i32[:n]
+    got = dict(pos=f[:, L.o_pos:L.o_pos + 4].reshape(n, 2, 2), vel=f[:, L.o_vel:L.o_vel + 4].reshape(n, 2, 2),
+               angle=f[:, L.o_angle:L.o_angle + 2], angvel=f[:, L.o_angvel:L.o_angvel + 2])
+    worst = np.zeros(n)
+    for key, g in got.items():
+        ref = fx['after_' + key][rows]
+        with np.errstate(invalid='ignore'):
+            d = np.abs(g - ref)
+        d = np.where(np.isnan(g) & np.isnan(ref), 0.0, d)
+        d = np.where(g == ref, 0.0, d)   # (equal infinities)
+        d = np.where(np.isnan(d), np.inf, d)
+        worst = np.maximum(worst, d.reshape(n, -1).max(axis=1))
+    fl = q[:, L.o_flags:L.o_flags + 2]
+    flags_ok = (np.all(((fl & _abi.MOOG_F_VEL_F32) != 0) == (fx['after_vel_f32'][rows] != 0), axis=1) &
+                np.all(((fl & _abi.MOOG_F_ANGVEL_F32) != 0) == (fx['after_angvel_f32'][rows] != 0), axis=1) &
+                np.all((fl & _abi.MOOG_F_ALIVE) != 0, axis=1))
+    return worst, flags_ok
+
+
+PAIR_TOL = 1e-9   # the bar collisions_kat.npz is held to
+
+
+def assert_pairs(c, f64, i32, fx, rows, who):
+    """The assertion shared by the oracle test and the HIP test; names the pairs that miss, with their class bits."""
+    worst, flags_ok = pair_errors(c, f64, i32, fx, rows)
+    faults = i32[:len(rows), c.layout.o_fault]
+    bad = np.flatnonzero((worst > PAIR_TOL) | ~flags_ok | (faults != 0))
+    names = [str(x) for x in fx['classes']]
+    report = ['pair %d (error %.3g, flags %s, fault %d): %s' % (
+        rows[i], worst[i], 'ok' if flags_ok[i] else 'DIFFER', faults[i],
+        ' '.join(nm for k, nm in enumerate(names) if (int(fx['cls'][rows[i]]) >> k) & 1)) for i in bad[:12]]
+    print('%s: %d pairs, worst |%s - reference| %.3g' % (who, len(rows), who, float(worst.max())))
+    assert len(bad) == 0, '%d of %d pairs differ from the reference:\n%s' % (len(bad), len(rows), '\n'.join(report))
+    return float(worst.max())
+
+
 # files named like a recording that hold one but have a test of their own (tests/test_views_gpu.py, tests/test_views.py: the
 # several-observer recordings of tests/golden/make_golden_views.py) -- named one by one, so that no new file hides behind a pattern
 RECORDINGS_WITH_OWN_TESTS = (('views_zoo_l0', 0), ('views_zoo_l1', 0), ('views_zoo_l2', 0))
