@@ -151,7 +151,11 @@ extern __shared__ __attribute__((aligned(16))) unsigned char moog_lds[];
 #define EP(e_) ((e_).P)
 #define EFOP(e_, k) (&(e_).fops[k])
 #define ENFOPS(e_) ((e_).n_fops)
+#ifdef MOOG_PROFILE   // (bits 8 - 12 of the word select the section to report there: the switches 512 and 1024 are not read)
+#define EDBG(e_) ((e_).dbg & ~0x1f00)
+#else
 #define EDBG(e_) ((e_).dbg)
+#endif
 #define EF(e_) ((e_).f)
 #define EQ(e_) ((e_).q)
 #define EBB(e_) ((e_).bb)
@@ -659,6 +663,23 @@ __device__ __forceinline__ int nth_set_bit32(unsigned m, int k) {
 // 30-gons never fit sixteen lanes and each of its candidates takes the whole wave's path test -- is exact too, and was not
 // faster (profiles/r05_step_experiments.txt: falling_balls_64 +0.7 %, colliding_predators_32 -2 %).
 // `pr0`: the pair (s0 << 8 | s1) of this lane's group -- candidate k of the batch in the lanes of group k -- or CAND_SKIP.
+// Returns the prefix length in bits 0 - 7 and the flags of bits 8 / 9 / 10 (below), and in two masks of one bit per group
+// (64 / G of them; both empty when the first candidate alone sends the batch to the ordinary path) the outcome of EVERY
+// group, those behind the one that ends the prefix too -- all groups are evaluated at once anyway:
+//   bits 16 + g  "rejected": group g is active (a pair, g < n) and none of its lanes saw a hit or was slow;
+//   bits 20 + g  "exchangeable": rejected, and none of its lanes saw two parallel edges (segments_intersect_kind 4).
+// collision_same_layer strikes pairs by them; why that cannot move a result:
+//  - A rejected group means its pair does not overlap: paths_intersect_filled would return false for it on the current state,
+//    decided by the edge tests alone (the `slow` filter has sent every pair whose containment tests could run, and every pair
+//    with a NaN box, to the ordinary path).  collision_step would return before touching anything -- what skipping the prefix
+//    has always relied on --, and that stays true until one of the two sprites is touched.
+//  - An exchangeable group gives the same answer for the exchanged pair: the culls and the slow / big / total > G conditions
+//    are symmetric in the two polygons as a set, the edge pairs tested are the same set, and segments_intersect_kind's answers
+//    0 and 2 are unchanged under exchange (the comment above it); only its parallel branch (1, 4) is not symmetric.  With no
+//    hit and no 4 in the group every edge pair answered 0, and answers 0 the other way round.  A group that did see a 4 has
+//    only its own bit struck; its mirror image is tested in its turn.
+//  - The pairs are still visited in the reference's order: a strike only removes a visit that would change nothing, and a
+//    pair behind the cursor is never revisited, as before.
 template <int G>
 __device__ inline int narrow_reject_prefix_g(const Env& e, int pr0, int n) {
   constexpr int SH = G == 16 ? 4 : 5;
@@ -723,15 +744,22 @@ __device__ inline int narrow_reject_prefix_g(const Env& e, int pr0, int n) {
     }
   }
   const unsigned long long stop = __ballot((hit & 3) != 0 || slow), slows = __ballot(slow), props = __ballot(hit == 2);
+  const unsigned long long pars = __ballot(hit == 4), acts = __ballot(active);   // (active: the same in all lanes of a group)
   int r = 0;
+#pragma unroll
+  for (int g = 0; g < 64 / G; ++g)
+    if (((acts >> (G * g)) & 1ull) != 0ull && ((stop >> (G * g)) & GM) == 0ull)
+      r |= (0x10000 << g) | ((((pars >> (G * g)) & GM) == 0ull) ? 0x100000 << g : 0);
+  const int masks = r;
+  r = 0;
   while (r < n && ((stop >> (G * r)) & GM) == 0ull) ++r;
   // bit 8: the candidate that ended the prefix is a proven overlap (its edges cross); bit 9: two non-parallel edges do
-  if (r == n) return r | 1024;   // bit 10: every candidate looked at is rejected (n of them: four, or two of the long ones)
+  if (r == n) return r | 1024 | masks;   // bit 10: every candidate looked at is rejected (n of them: four, or two of the long ones)
   if (((slows >> (G * r)) & GM) == 0ull) {
     if ((props >> (G * r)) & GM) r |= 512;
     r |= 256;
   }
-  return r;
+  return r | masks;
 }
 
 __device__ inline int narrow_reject_prefix(const Env& e, int pr0, int n) {
@@ -1515,9 +1543,10 @@ __device__ inline void resolve_contact(Env& e, double elasticity, int s0, int s1
   }
 }
 
-// collisions.py:494-584.  Returns true when a sprite position changed (the broad
-// phase must then be redone for the following pairs); velocity-only outcomes and
-// "future contact" no-ops return false.
+// collisions.py:494-584.  Returns true when the call touched a sprite -- a resolved contact (positions, velocities, angular
+// velocities: resolve_contact) or a _make_disjoint that moved the pair -- so that the broad phase is redone for the pairs of
+// the two sprites and what collision_same_layer has struck about them is forgotten; false exactly when the state is as it
+// was: no overlap, a "future contact" no-op, a _make_disjoint that left the pair alone.  The strikes lean on that.
 // `known_hit`: the caller has already seen the two paths intersect on the current state
 // `mirror_noop` (when given): set when this call changed nothing AND the call with s0 and s1 exchanged would change
 // nothing either as long as neither sprite is touched: either the paths do not overlap, by tests that are symmetric in the
@@ -2233,6 +2262,9 @@ __device__ inline void collision_same_layer(Env& e, const CollP& F, int a0, int 
   // contact" both ways round (collision_step's mirror_noop), and neither sprite has been touched since.  The reference
   // visits both orders (physics.py:103-108); in the contact-heavy envs that set the kernel's duration three searches in
   // four end "future contact", and a pair that overlaps without colliding does so twice in every sub-step.
+  // Likewise the pairs a narrow batch has rejected, and their mirror images (below, after the batch): about nine candidates
+  // in ten.  Debug bit 512 switches the strikes after collision_step off, bit 1024 those after a batch (generic kernels;
+  // not in a -DMOOG_PROFILE build, where these bits belong to the section selector: EDBG).
   unsigned long long skipbits = 0ull;
   const bool use_skip = !uni(EP(e)->vel_alias);   // (velocity arrays shared across sprites: a contact elsewhere may touch the pair)
   // The cursor (wave uniform): every ordered pair before (a0 + crow, a0 + ccol) has been dealt with.  ccol < n <= 64.
@@ -2273,6 +2305,29 @@ __device__ inline void collision_same_layer(Env& e, const CollP& F, int a0, int 
 #ifdef MOOG_COUNT_PREFIX   // (analysis builds: batches in the make_disjoint counter, tools/heavy_bench.py)
       if (EDBG(e) & 128) { e.n_disj += 1 + 1000 * nn; }
 #endif
+      // What the batch decided is struck before the candidate that ended the prefix goes to collision_step (whose contact,
+      // if any, makes the pairs of its two sprites live again below).  Every rejected group, those behind the prefix too:
+      // the pair's own bit, so that the next batches do not test it again; when the group is exchangeable and the mirror
+      // image comes later in this sub-step, the mirror's bit as well (narrow_reject_prefix_g has the argument).  A struck pair
+      // is one bit in one lane and leaves no hole: the cursor walks row & ~skipbits.
+      // (Round 4 formed batches around such holes in the LDS candidate list and lost 4 %, profiles/r04_fn_bench.txt.)
+      if (use_skip && !(EDBG(e) & 1024)) {
+        const int rejm = (rr >> 16) & 15, exm = (rr >> 20) & 15;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if ((rejm >> k) & 1) {
+            const int pk = k == 0 ? p0 : (k == 1 ? p1 : (k == 2 ? p2 : p3));
+            const int ks = (pk >> 8) - a0, kt = (pk & 255) - a0;
+            if (e.lane == ks) skipbits |= 1ull << kt;
+            if (((exm >> k) & 1) && kt > ks) {
+              if (e.lane == kt) skipbits |= 1ull << ks;
+#ifdef MOOG_COUNT_PREFIX   // (mirror images struck: the millions of the same counter)
+              if (EDBG(e) & 128) e.n_disj += 1000000;
+#endif
+            }
+          }
+        }
+      }
       SEC(e, SEC_CONSUME);
       PROF_ADD(e, 8);
       rejected = (rr & 1024) != 0;   // all of them: the cursor passes the last one, on to the next batch

@@ -13,6 +13,7 @@ mkdir -p $B
 OBJS=""
 for u in f3 f4 t3 t4 m3 m4; do
   if [ $u = $UNIT ]; then OBJS="$OBJS $B/step_${UNIT}_$NAME.o"; else OBJS="$OBJS $L/moog_step_$u.o"; fi
+  OBJS="$OBJS $L/moog_step_${u}r.o"   # (the action-repeat units: the shipped ones)
 done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $OBJS $L/moog_reset_r0.o $L/moog_reset_r1.o $L/moog_engine.o $L/moog_raster.o \
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $OBJS $L/moog_reset_r0.o $L/moog_reset_r1.o $L/moog_engine.o $L/moog_raster.o $L/moog_sprite_table.o \
   -o $B/libmoog_$NAME.so && echo built $B/libmoog_$NAME.so

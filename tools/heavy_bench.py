@@ -9,6 +9,14 @@ identical from run to run (the step path draws no random numbers on this workloa
 
     python tools/heavy_bench.py capture [workload]      -> gpurun_out/heavy_<workload>.npz  (copy to tools/ubench/)
     python tools/heavy_bench.py bench [workload] [--sections]
+
+With COUNT_PREFIX=1 and a -DMOOG_COUNT_PREFIX build of the step unit (bash tools/build_variant.sh count -DMOOG_COUNT_PREFIX,
+MOOG_HIP_LIB=tools/ubench/build/libmoog_count.so) `bench` also prints the narrow batches of collision_same_layer /
+collision_layer_pair per env-step, the candidates in them and the mirror images struck after a batch, once with the strikes
+a batch allows (moog_device.h collision_same_layer) and once without them (debug bit 1024).  RANDOM_SAMPLE=1 replays the
+random sample of envs instead of the heaviest.
+(--sections needs a -DMOOG_PROFILE build and selects the section in bits 8 - 12 of the debug word; such a build does not
+read the switches 512 and 1024 there, so every section is measured with all strikes on.)
 """
 import os, sys
 R = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
@@ -87,8 +95,14 @@ for n in ([int(os.environ['HEAVY_ONLY'])] if os.environ.get('HEAVY_ONLY') else (
     print('%s x %d envs (%d distinct heavy envs): cycles mean %.0f  p50 %.0f  max %.0f   call %.0f us   path tests %.1f searches %.1f' % (
         name, n, m, c.mean(), np.median(c), c.max(), us, (cnt % 100000).mean(), (cnt // 100000).mean()))
     if os.environ.get('COUNT_PREFIX'):
-        d3 = r // 1e10
-        print('   batches per env-step %.1f, candidates in them %.1f, rejected symmetrically %.1f' % ((d3 % 1000).mean(), ((d3 // 1000) % 1000).mean(), (d3 // 1000000).mean()))
+        for label, dbg in (('batch strikes on ', 128), ('batch strikes off', 128 | 1024)):
+            env.set_debug(dbg, 0)
+            env.state_f64.copy_(f); env.state_i32.copy_(q)
+            ts = env.step(a)
+            torch.cuda.synchronize()
+            cc, d3 = ts.discount.cpu().numpy(), ts.reward.cpu().numpy() // 1e10
+            print('   %s: batches per env-step %.1f, candidates in them %.1f, mirror images struck after a batch %.1f; cycles mean %.0f max %.0f' % (
+                label, (d3 % 1000).mean(), ((d3 // 1000) % 1000).mean(), (d3 // 1000000).mean(), cc.mean(), cc.max()))
     if os.environ.get('MOOG_WATCH') == '1':   # section samples of the watcher wavefronts (a -DMOOG_WATCH build of the step kernel)
         import ctypes
         SECN = ['prologue', 'rules + action', 'force loop', 'same layer: broad rounds', 'same layer: list', 'same layer: batch formation',
