@@ -52,6 +52,7 @@ extern "C" {
 #define MOOG_NUM_FACTORS 14
 #define MOOG_MAX_VIEWS 4     /* PILRenderer observers one engine draws: the program's render + 3 extra views (moog_engine_add_view) */
 #define MOOG_MAX_TABLES 4    /* SpriteTable observers one engine writes (moog_engine_add_table) */
+#define MOOG_MAX_SEGMENTATIONS 2   /* Segmentation observers one engine draws (moog_engine_add_segmentation) */
 #define MOOG_MAX_TABLE_COLS 17 /* columns of one table: MOOG_TCOL_COUNT */
 #define MOOG_MAX_HDRAWS 32   /* draws a state_initializer takes from np.random directly (per reset) */
 #define MOOG_MAX_OP_DRAWS 24 /* draws of one generation op: its sampled factors + the direct draws made between them */
@@ -725,11 +726,23 @@ typedef struct {
   int32_t row_slot[MOOG_MAX_SLOTS];
 } moog_table_t;
 
+/* A segmentation (the Segmentation observer): one [n_envs][height][width] uint8 image of sprite ids, drawn on the device like
+ * a view's frame.  slot_id[s] is what a pixel shows when sprite slot s is the last-drawn sprite with opacity > 0 that covers
+ * it (0: the slot occludes and shows as background).  The modifier fields are moog_render_t's. */
+typedef struct {
+  int32_t height, width;   /* 1 .. 128 each (the mask rasteriser's frames) */
+  int32_t polymod;         /* MOOG_POLYMOD_* */
+  int32_t polymod_layer;   /* FIRST_PERSON: agent layer */
+  int32_t n_slots;         /* the program's n_slots */
+  uint8_t slot_id[MOOG_MAX_SLOTS];
+} moog_segmentation_t;
+
 /* kernel ids for moog_engine_kernel_time() */
 /* MOOG_K_TABLES: the one launch that writes a call's sprite tables (moog_engine_add_table). */
 /* MOOG_K_RASTER: the program's own frames (views[0]); MOOG_K_VIEWS: everything the extra views of moog_engine_add_view cost a
  * call -- their one derive launch (which also derives the primary's records when a render call needs them) and their raster,
- * crop and resize launches */
+ * crop and resize launches; the segmentations of moog_engine_add_segmentation are timed under MOOG_K_VIEWS too, one bracket
+ * per call around their derive launch and their raster and crop launches */
 enum { MOOG_K_STEP = 0, MOOG_K_RASTER = 1, MOOG_K_RESET = 2, MOOG_K_VIEWS = 3, MOOG_K_TABLES = 4, MOOG_K_COUNT = 5 };
 
 int moog_abi_version(void);
@@ -816,6 +829,28 @@ int moog_engine_view_raster_path(moog_engine_t* e, int32_t view, int32_t* path);
 int moog_engine_add_table(moog_engine_t* e, const moog_table_t* table_desc, int32_t* table);
 int moog_engine_set_table_buffer(moog_engine_t* e, int32_t table, void* table_dev);
 int moog_engine_observe_tables(moog_engine_t* e, void* hip_stream);
+
+/* Segmentations.  Ground-truth instance masks of the frame an agent sees: per pixel the id of the sprite visible there.  The
+ * reference has no such observer; what it would draw is defined through its renderer -- pil_renderer.py:100-118 with every
+ * polygon's colour replaced by (id, 0, 0) and its opacity by 255, polygons of opacity 0 left out, channel 0 of the result.
+ * moog_engine_add_segmentation adds one to the engine and returns its index (0 .. MOOG_MAX_SEGMENTATIONS - 1) in *index.  Like
+ * views and tables it belongs to the engine handle, never to the program: its bytes, its hash and the step kernels do not know
+ * about it.  Coverage is the mask rasteriser's, i.e. exactly Pillow's ImageDraw.polygon on the integer points the renderer
+ * would draw, in the reference's drawing order (layers in state order, sprites in list order; a torus copy carries its
+ * sprite's id); rows are flipped as the frames' are, so a segmentation and a frame of the same size and modifier align pixel
+ * for pixel.  Every sprite is drawn (no cached prefix picture).
+ * MOOG_E_INVALID: a program that draws no frames (render 0 x 0: its engine has no raster state), height or width outside
+ * 1 .. 128 (larger frames are the span rasteriser's, which draws no ids), n_slots that is not the program's, a modifier out of
+ * range.  MOOG_E_UNSUPPORTED: a frame of that size and modifier that the mask rasteriser cannot hold
+ * (moog_engine_raster_path's criteria: more than 256 items, or tables beyond 64 KB of LDS), or one beyond
+ * MOOG_MAX_SEGMENTATIONS.
+ * moog_engine_set_segmentation_image binds the device buffer [n_envs][height][width] (borrowed; NULL unbinds).  Every call that
+ * draws the primary's frames (moog_engine_reset / moog_engine_step with out->image, moog_engine_render) also draws every bound
+ * segmentation, from the records as the call left them: one derive launch for all of them (their draw records are always
+ * derived, never written by the step kernel), one raster launch each, and a crop launch for a width that is no multiple of
+ * 16 -- timed under MOOG_K_VIEWS.  An engine without a bound segmentation launches nothing and pays one comparison. */
+int moog_engine_add_segmentation(moog_engine_t* e, const moog_segmentation_t* seg, int32_t* index);
+int moog_engine_set_segmentation_image(moog_engine_t* e, int32_t index, uint8_t* ids_dev);
 
 /* Optional launch-order schedule for the step kernel (pure performance hint, results do
  * not depend on it).  `cost_dev` (float[n_envs], borrowed; zeroed by this call) holds a moving average of every env's

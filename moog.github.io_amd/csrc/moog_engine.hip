@@ -82,6 +82,15 @@ struct STable {
   int32_t* d_rows = nullptr;
 };
 
+// A segmentation of the engine (moog_engine_add_segmentation): the raster state of a view of its size and modifier (always on
+// the mask path, no cached prefix), the ids its emitter puts where a view's emitter puts colours, and the bound image, or null.
+struct SegView {
+  RView v;
+  uint32_t* d_ids = nullptr;   // [n_envs][slots] the emitter's rgb_override: slot_id in the low byte (replicated per env: the emitter indexes it by env)
+  uint8_t* ids = nullptr;      // [n_envs][height][width] (moog_engine_set_segmentation_image)
+  uint8_t* pad_ids = nullptr;  // [n_envs][height][pad_w] when the width is no multiple of 16 (cropped into `ids`)
+};
+
 struct moog_engine {
   moog_program_t prog;
   moog_layout_t L;
@@ -111,6 +120,8 @@ struct moog_engine {
   int n_views = 1;               // views[0] and the extra views added so far
   STable tables[MOOG_MAX_TABLES];
   int n_tables = 0, n_bound_tables = 0;   // tables added so far; how many of them have a buffer
+  SegView segs[MOOG_MAX_SEGMENTATIONS];
+  int n_segs = 0, n_bound_segs = 0;       // segmentations added so far; how many of them have an image
   bool frameless = false;        // render 0 x 0: the program draws no frames (no raster state at all)
   uint8_t* aa_canvas = nullptr;   // shared by the anti-aliased views: [aa_chunk][canvas_h][pad_w][3] of whichever is drawn
   uint8_t* aa_tmp = nullptr;      // [aa_chunk][canvas_h][width rounded up to 4][3]
@@ -171,6 +182,12 @@ static void free_engine(moog_engine* e) {
     if (v.rows_seen) hipHostFree(v.rows_seen);
   }
   for (STable& t : e->tables) if (t.d_rows) hipFree(t.d_rows);
+  for (SegView& g : e->segs) {
+    if (g.v.draw) hipFree(g.v.draw);
+    if (g.v.rows_seen) hipHostFree(g.v.rows_seen);
+    if (g.d_ids) hipFree(g.d_ids);
+    if (g.pad_ids) hipFree(g.pad_ids);
+  }
   if (e->s_f64) hipFree(e->s_f64);
   if (e->s_i32) hipFree(e->s_i32);
   if (e->aa_canvas) hipFree(e->aa_canvas);
@@ -1091,11 +1108,42 @@ static bool derives_ahead(moog_engine* e, const RView& v) {
   return v.aa <= 1 || v.aa_chunk >= e->n_envs;
 }
 
+// Every bound segmentation of the engine from the records as they are on stream s, under one MOOG_K_VIEWS bracket: one derive
+// launch for the draw records of all of them (the emitter with the ids as its per-slot colours, no static prefix), then per
+// segmentation the ids kernel and, for a width that is no multiple of 16, the crop.  An engine without a bound segmentation
+// returns at the first comparison.
+static int launch_segmentations(moog_engine* e, hipStream_t s) {
+  if (e->n_bound_segs == 0) return MOOG_OK;
+  Bracket br(e, MOOG_K_VIEWS, s);
+  RmEmit em[MOOG_MAX_SEGMENTATIONS];
+  RArgs r[MOOG_MAX_SEGMENTATIONS];
+  SegView* sv[MOOG_MAX_SEGMENTATIONS];
+  int n = 0;
+  for (int k = 0; k < e->n_segs; ++k) {
+    SegView& g = e->segs[k];
+    if (!g.ids) continue;
+    r[n] = raster_args(e, g.v, g.pad_ids ? g.pad_ids : g.ids);
+    r[n].em.rgb_override = g.d_ids; r[n].em.n_static = 0;
+    r[n].rgb_override = g.d_ids; r[n].draw_ready = 1;
+    em[n] = r[n].em;
+    sv[n++] = &g;
+  }
+  moog_derive_launch(em, n, r[0], s);
+  for (int k = 0; k < n; ++k) {
+    moog_segmentation_launch(r[k], s);
+    const RView& v = sv[k]->v;
+    if (sv[k]->pad_ids) moog_crop_launch(sv[k]->pad_ids, sv[k]->ids, (size_t)e->n_envs * v.canvas_h, v.pad_w, v.canvas_w, s);
+  }
+  HIPCHK(hipGetLastError());
+  return MOOG_OK;
+}
+
 // Every view's frames of one call: the primary's into `image` (timed as MOOG_K_RASTER, exactly as an engine without extra
 // views draws them), then -- under MOOG_K_VIEWS -- one derive launch for the draw records of every extra view on the mask path
 // (and of the primary, when its records were not written by the step kernel), the extra views' raster launches, and the
 // primary's raster launch behind them.
 static int launch_frames(moog_engine* e, uint8_t* image, hipStream_t s, bool draw_ready = false, int timed = -1) {
+  { const int rc = launch_segmentations(e, s); if (rc) return rc; }
   RView* extra[MOOG_MAX_VIEWS];
   int n_extra = 0;
   for (int k = 1; k < e->n_views; ++k) if (e->views[k].image) extra[n_extra++] = &e->views[k];
@@ -1467,6 +1515,69 @@ int moog_engine_set_view_image(moog_engine_t* e, int32_t view, uint8_t* image_de
   if (!e) return fail(MOOG_E_INVALID, "null engine");
   if (view < 1 || view >= e->n_views) return fail(MOOG_E_INVALID, "no such extra view (the primary's frames are the calls' own image)");
   e->views[view].image = image_dev;
+  return MOOG_OK;
+}
+
+int moog_engine_add_segmentation(moog_engine_t* e, const moog_segmentation_t* seg, int32_t* index) {
+  if (!e || !seg || !index) return fail(MOOG_E_INVALID, "null argument");
+  if (e->frameless) return fail(MOOG_E_INVALID, "this program draws no frames (render 0 x 0): its engine has no raster state and takes no segmentation");
+  if (e->n_segs >= MOOG_MAX_SEGMENTATIONS) return fail(MOOG_E_UNSUPPORTED, "at most MOOG_MAX_SEGMENTATIONS segmentations per engine");
+  if (seg->width < 1 || seg->width > 128 || seg->height < 1 || seg->height > 128)
+    return fail(MOOG_E_INVALID, "segmentation size out of range (1 <= height, width <= 128: larger frames are the span rasteriser's, which draws no ids)");
+  if (seg->n_slots != e->prog.n_slots) return fail(MOOG_E_INVALID, "segmentation n_slots is not the program's");
+  moog_render_t render;
+  memset(&render, 0, sizeof render);
+  render.width = seg->width; render.height = seg->height; render.cmap = MOOG_CMAP_IDENTITY; render.aa = 1;
+  render.polymod = seg->polymod; render.polymod_layer = seg->polymod_layer;
+  int rc = validate_render(&e->prog, &render);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(e->device));
+  SegView& g = e->segs[e->n_segs];
+  g = SegView();
+  g.v.render = render;
+  g.v.P = e->d_prog;   // (the emitter reads the slots' vertex offsets from it; `render` is the span kernel's business)
+  rc = setup_view(e, g.v, false);
+  if (rc == MOOG_OK && !g.v.mask_setup.ok)
+    rc = fail(MOOG_E_UNSUPPORTED, "a frame of this size and modifier is not the mask rasteriser's (more than 256 items, or tables beyond 64 KB of LDS): no segmentation");
+  if (rc == MOOG_OK) {
+    const size_t slots = (size_t)e->prog.n_slots;
+    std::vector<uint32_t> ids((size_t)e->n_envs * slots);
+    for (size_t env = 0; env < (size_t)e->n_envs; ++env)
+      for (size_t sl = 0; sl < slots; ++sl) ids[env * slots + sl] = seg->slot_id[sl];
+    if (hipMalloc(&g.d_ids, ids.size() * sizeof(uint32_t)) != hipSuccess ||
+        hipMemcpy(g.d_ids, ids.data(), ids.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
+      rc = fail(MOOG_E_NOMEM, "hipMalloc(segmentation ids) failed");
+  }
+  if (rc == MOOG_OK && g.v.pad_w != g.v.canvas_w &&
+      hipMalloc(&g.pad_ids, (size_t)e->n_envs * g.v.canvas_h * g.v.pad_w) != hipSuccess)
+    rc = fail(MOOG_E_NOMEM, "hipMalloc(16-aligned segmentation) failed");
+  if (rc == MOOG_OK) {   // (the kernels' LDS limit is process-wide and only grows: moog_raster_configure_mask)
+    const hipError_t err = (hipError_t)moog_raster_configure_mask(64 * 1024);
+    if (err != hipSuccess) rc = fail(MOOG_E_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(err));
+  }
+  if (rc) {
+    const std::string msg = g_err;
+    (void)hipGetLastError();
+    if (g.v.draw) hipFree(g.v.draw);
+    if (g.v.rows_seen) hipHostFree(g.v.rows_seen);
+    if (g.d_ids) hipFree(g.d_ids);
+    if (g.pad_ids) hipFree(g.pad_ids);
+    g = SegView();
+    g_err = msg;
+    return rc;
+  }
+  *index = e->n_segs++;
+  return MOOG_OK;
+}
+
+int moog_engine_set_segmentation_image(moog_engine_t* e, int32_t index, uint8_t* ids_dev) {
+  if (!e) return fail(MOOG_E_INVALID, "null engine");
+  if (index < 0 || index >= e->n_segs) return fail(MOOG_E_INVALID, "no such segmentation");
+  SegView& g = e->segs[index];
+  if (!g.pad_ids && ((uintptr_t)ids_dev & 15))   // (the ids kernel stores 16 pixels at a time straight into it)
+    return fail(MOOG_E_INVALID, "segmentation image must be 16-byte aligned");
+  e->n_bound_segs += (ids_dev ? 1 : 0) - (g.ids ? 1 : 0);
+  g.ids = ids_dev;
   return MOOG_OK;
 }
 

@@ -163,6 +163,8 @@ int moog_raster_configure(size_t lds_bytes);   // hipFuncSetAttribute(max dynami
 void moog_raster_launch(const RArgs& a, size_t lds_bytes, hipStream_t stream);
 // the draw records of n_em (<= MOOG_MAX_VIEWS) views, derived from the records of `a` (P, L, f64, i32, vinfo, n_envs, env0) in one launch
 void moog_derive_launch(const RmEmit* em, int n_em, const RArgs& a, hipStream_t stream);
+// the id image of a segmentation view on the mask path (a.ms.ok), from draw records derived ahead: [n_envs][canvas_h][canvas_w] bytes into a.image
+void moog_segmentation_launch(const RArgs& a, hipStream_t stream);
 // Per-env prefix check: one wavefront per env compares the first n_static slots of the live record (alive bit, vertex count,
 // opacity, colour, live vertices) with the env's snapshot.  Different, or no picture yet (valid[env] == 0): the record is
 // copied to the snapshot, build[env] = 1, valid[env] = 1; equal: build[env] = 0.  A change in the middle of an episode

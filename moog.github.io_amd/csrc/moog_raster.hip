@@ -55,6 +55,12 @@ void moog_derive_launch(const RmEmit* em, int n_em, const RArgs& a, hipStream_t 
   moog_draw_derive_launch(d, stream);
 }
 
+// A segmentation view's id image (moog_engine_add_segmentation): the mask rasteriser's phases with rm_p5_ids, on draw records
+// derived ahead (moog_derive_launch with the view's id array as the emitter's rgb_override).  a.image: [n_envs][canvas_h][canvas_w] bytes.
+void moog_segmentation_launch(const RArgs& a, hipStream_t stream) {
+  moog_raster_ids_launch(mask_args(a), a.ms.lds, stream);
+}
+
 // Ordinary frames of programs the mask rasteriser takes (RmSetup::ok) are drawn by it; the pictures of the static / per-env
 // prefix, frames on top of a per-env prefix and every other program's frames by the push / sort / span kernel.
 void moog_raster_launch(const RArgs& a, size_t lds_bytes, hipStream_t stream) {

@@ -67,6 +67,62 @@ __global__ __launch_bounds__(RM_THREADS, RM_WAVES_PER_SIMD) void moog_raster_mas
   }
 }
 
+// The segmentation views' kernel (moog_engine_add_segmentation): the frame above through p4 -- load, row records, edges and
+// census, row sort, coverage masks, several passes -- and rm_p5_ids where that one composes colours: `a.image` is one byte per
+// pixel, [n_envs][H][W].  A kernel of its own, so that the frames' kernels keep their code and registers.  A segmentation has
+// no cached prefix picture (n_static = 0): s_lo is 0.
+template <int WORDS, bool BIG, bool COMPACT>
+__global__ __launch_bounds__(RM_THREADS, RM_WAVES_PER_SIMD) void moog_raster_ids_kernel(RmArgs a) {
+  const RmCtx c = rm_ctx(a.plan, moog_lds);
+  const int tid = (int)threadIdx.x, lane = tid & 63;
+  const int env = (int)blockIdx.x;
+  if (env >= a.n_envs) return;
+  rm_load(a, c, env, tid, RM_THREADS);
+  __syncthreads();
+  if (a.debug_stop == 1 || a.debug_stop == 2) return;
+  const int s_lo = 0;
+  const bool single = __builtin_amdgcn_readfirstlane(c.misc[6]) != 0;
+  if (a.rows_seen && tid == 0 && c.rowoff[a.S] > a.cap_rows) {
+    atomicMax(a.rows_seen, c.rowoff[a.S]);
+    atomicAdd(a.rows_seen + 1, 1);
+  }
+  for (int base = 0;;) {
+    const int end = __builtin_amdgcn_readfirstlane(rm_pass_end(a, c, base));
+    const int total_rows = __builtin_amdgcn_readfirstlane(c.rowoff[end] - c.rowoff[base]);
+    if (!single) {
+      rm_p2_assign(a, c, base, end, s_lo, lane);
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    }
+    if (a.debug_stop == 3) return;
+    rm_p3<WORDS, COMPACT>(a, c, base, end, s_lo, tid, RM_THREADS);
+    __syncthreads();
+    if (a.debug_stop == 4) return;
+    if (a.cap_rows <= RM_SORT_ROUNDS * RM_THREADS) {
+      RmSortKey sk;
+      rm_p4a(c, total_rows, tid, RM_THREADS, sk);
+      __syncthreads();
+      rm_p4b(c, total_rows, tid, RM_THREADS, sk);
+      __syncthreads();
+    } else {
+      rm_p4a_lds(c, total_rows, tid, RM_THREADS);
+      __syncthreads();
+      rm_p4b_lds(c, total_rows, tid, RM_THREADS);
+      __syncthreads();
+    }
+    rm_p4<WORDS, COMPACT>(a, c, total_rows, tid, RM_THREADS, c.xx + (tid >> 6) * a.plan.xx_stride);
+    if (BIG) rm_p4_big<WORDS, COMPACT>(a, c, tid, RM_THREADS, c.xx + (tid >> 6) * a.plan.xx_stride, reinterpret_cast<uint8_t*>(c.xx + (RM_THREADS / 64) * a.plan.xx_stride));
+    __syncthreads();
+    if (a.debug_stop == 5) return;
+    rm_p5_ids<WORDS>(a, c, env, base == 0, tid, RM_THREADS);
+    if (end >= a.S) break;
+    base = end;
+    __syncthreads();
+    rm_next_pass(a, c, tid, RM_THREADS);
+    __syncthreads();
+  }
+}
+
 // The draw records of frames the engine did not step itself (moog_engine_render after load_state or an edit of the state
 // tensors, resets, programs whose step kernels do not emit, the extra views of moog_engine_add_view): one wavefront per env
 // runs the emitter on the record in HBM, once per view -- the primary's and every extra view's records in one launch.
@@ -99,16 +155,32 @@ static inline moog_raster_mask_fn moog_raster_mask_pick(int words, bool big, boo
   return table[words - 1][big ? 1 : 0][compact ? 1 : 0];
 }
 
+static inline moog_raster_mask_fn moog_raster_ids_pick(int words, bool big, bool compact) {
+  static const moog_raster_mask_fn table[2][2][2] = {
+      {{moog_raster_ids_kernel<1, false, false>, moog_raster_ids_kernel<1, false, true>},
+       {moog_raster_ids_kernel<1, true, false>, moog_raster_ids_kernel<1, true, true>}},
+      {{moog_raster_ids_kernel<2, false, false>, moog_raster_ids_kernel<2, false, true>},
+       {moog_raster_ids_kernel<2, true, false>, moog_raster_ids_kernel<2, true, true>}}};
+  return table[words - 1][big ? 1 : 0][compact ? 1 : 0];
+}
+
 static inline int moog_raster_mask_configure(size_t lds_bytes) {
   hipError_t err = hipSuccess;
   for (int k = 0; k < 8 && err == hipSuccess; ++k)
     err = hipFuncSetAttribute(reinterpret_cast<const void*>(moog_raster_mask_pick(1 + (k & 1), (k & 2) != 0, (k & 4) != 0)),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+  for (int k = 0; k < 8 && err == hipSuccess; ++k)
+    err = hipFuncSetAttribute(reinterpret_cast<const void*>(moog_raster_ids_pick(1 + (k & 1), (k & 2) != 0, (k & 4) != 0)),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
   return (int)err;
 }
 
 static inline void moog_raster_mask_launch(const RmArgs& a, size_t lds_bytes, hipStream_t stream) {
   hipLaunchKernelGGL(moog_raster_mask_pick(a.W > 64 ? 2 : 1, a.big != 0, a.compact != 0), dim3((unsigned)a.n_envs), dim3(RM_THREADS), lds_bytes, stream, a);
+}
+
+static inline void moog_raster_ids_launch(const RmArgs& a, size_t lds_bytes, hipStream_t stream) {
+  hipLaunchKernelGGL(moog_raster_ids_pick(a.W > 64 ? 2 : 1, a.big != 0, a.compact != 0), dim3((unsigned)a.n_envs), dim3(RM_THREADS), lds_bytes, stream, a);
 }
 
 static inline void moog_draw_derive_launch(const RmDeriveArgs& d, hipStream_t stream) {

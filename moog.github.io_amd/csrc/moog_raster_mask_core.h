@@ -1048,6 +1048,48 @@ RM_FN void rm_p5(const RmArgs& a, const RmCtx& c, int env, bool first_pass, int 
   for (int seg = tid; seg < segs; seg += T) rm_p5_segment<WORDS, true>(a, c, out, first_pass, from_cache, seg, true);
 }
 
+// Four coverage bits -> the byte masks of four one-byte pixels (bit k -> byte k: the four shifted copies of the nibble do not
+// overlap, so nothing carries)
+RM_FN uint32_t rm_spread4(uint32_t nibble) { return ((nibble * 0x00204081u) & 0x01010101u) * 0xffu; }
+
+// p5 of a segmentation view (moog_engine_add_segmentation): the frame is one byte per pixel, the id of the last-drawn item
+// that covers the pixel and has opacity != 0 (Pillow's blend with alpha 0 leaves a pixel as it was); 0 where there is none.
+// The item's id comes in the low byte of its colour word (the emitter's rgb_override), its opacity where it always is.  One
+// 16-pixel segment = 16 bytes = one 128-bit store per thread; the segment's items in painter's order as in rm_p5_segment,
+// without a blend path.  first_pass: the picture starts from zeros, else from what `image` holds.
+template <int WORDS>
+RM_FN void rm_p5_ids(const RmArgs& a, const RmCtx& c, int env, bool first_pass, int tid, int T) {
+  const int nseg = a.W >> 4, segs = a.H * nseg;
+  uint8_t* out = a.image + (size_t)env * a.H * a.W;
+  for (int seg = tid; seg < segs; seg += T) {
+    const int y = seg / nseg, sg = seg - y * nseg, x0 = sg * 16;
+    RmU4* dst = reinterpret_cast<RmU4*>(out + (size_t)(a.flip ? a.H - 1 - y : y) * a.W + x0);   // (a multiple of 16)
+    RmU4 d = {0u, 0u, 0u, 0u};
+    if (!first_pass) d = *dst;
+    for (int iw = 0; iw < a.iwords; ++iw) {
+      uint32_t bitsw = c.seg[seg * a.iwords + iw];
+      // (wave-uniform loop, no branch inside: a lane without an item left paints with an empty mask)
+      if (RM_ANY(bitsw != 0u)) do {
+        const bool valid = bitsw != 0u;
+        const int g = valid ? iw * 32 + rm_ffs(bitsw) : 0;
+        bitsw &= bitsw - 1u;
+        const RmItem it = c.info[g];
+        const uint32_t* mrow = reinterpret_cast<const uint32_t*>(c.rows + (valid ? it.rowbase + y : 0));
+        const bool paints = valid && (it.rgba >> 24) != 0u;
+        const uint32_t bits = paints ? (mrow[x0 >> 5] >> (x0 & 31)) & 0xffffu : 0u;
+        const uint32_t idw = (it.rgba & 0xffu) * 0x01010101u;
+        const uint32_t m0 = rm_spread4(bits & 15u), m1 = rm_spread4((bits >> 4) & 15u), m2 = rm_spread4((bits >> 8) & 15u),
+                       m3 = rm_spread4(bits >> 12);
+        d.x = (idw & m0) | (d.x & ~m0);
+        d.y = (idw & m1) | (d.y & ~m1);
+        d.z = (idw & m2) | (d.z & ~m2);
+        d.w = (idw & m3) | (d.w & ~m3);
+      } while (RM_ANY(bitsw != 0u));
+    }
+    *dst = d;
+  }
+}
+
 // Later passes start from clean row records / segment words
 RM_FN void rm_next_pass(const RmArgs& a, const RmCtx& c, int tid, int T) {
   if (tid < 5) c.misc[8 + tid] = 0;

@@ -26,11 +26,15 @@ from .state_initialization import distributions as distribs
 
 Compiled = collections.namedtuple(
     'Compiled', ['program', 'layer_names', 'layer_slots', 'observer_key', 'layout', 'shape_names', 'rule_ref_index',
-                 'pstate_slots', 'dynamic_meta', 'color_fn', 'layer_n_init', 'views', 'tables', 'table_rows'])
+                 'pstate_slots', 'dynamic_meta', 'color_fn', 'layer_n_init', 'views', 'tables', 'table_rows',
+                 'segmentations', 'segmentation_rows'])
 # views: [(observer key, moog_render_t)] of the config's PILRenderers after the first, in dict order -- the engine's extra views
 # (moog_engine_add_view); never part of the program.  tables: [(observer key, moog_table_t)] of the config's SpriteTables, in dict
 # order -- the engine's sprite tables (moog_engine_add_table), never part of the program either; table_rows: {key: [(layer
-# name, index in layer)] per row}.  observer_key: the first PILRenderer's key, or None when the config has
+# name, index in layer)] per row}.  segmentations: [(observer key, moog_segmentation_t)] of the config's Segmentation observers, in
+# dict order -- the engine's segmentations (moog_engine_add_segmentation), never part of the program; segmentation_rows: {key:
+# [(layer name, index in layer)] per row}: mask value v of an 'instance' segmentation is row v - 1.
+# observer_key: the first PILRenderer's key, or None when the config has
 # none (the program's render is then 0 x 0: no frames).
 
 
@@ -364,6 +368,47 @@ def _flatten_host_rules(rules, out=None):
         if kids:
             _flatten_host_rules(list(kids), out)
     return out
+
+
+def mask_plan_bytes(items, points, width, height, cap_rows, big, compact):
+    """LDS bytes of the mask rasteriser's tables for one frame: csrc/moog_raster_mask_core.h rm_plan restated (two
+    wavefronts per frame; tests/test_segmentation_model.py holds it against the C function)."""
+    al = lambda x: (x + 15) & ~15
+    waves, iwords = 2, (items + 31) // 32
+    o = al(points * (4 if compact else 16))
+    o = al(o + points * 4)
+    o = al(o + cap_rows * 16)
+    o = al(o + cap_rows * 2)
+    o = al(o + items * 16)
+    o = al(o + items * 8)
+    o = al(o + (items + 1) * 4)
+    o = al(o + height * (width // 16) * iwords * 4)
+    o = al(o + 256)
+    o = al(o + waves * (256 if big else 64) * 4 + (waves * 64 * 32 if big else 0))
+    o = al(o + 64)
+    o = al(o + points)
+    o = al(o + (cap_rows * 2 if cap_rows > 3 * 128 else 0))
+    return al(o + max(waves * 64 * 4, cap_rows * 2))
+
+
+def segmentation_refusal(program, layout, seg):
+    """Why the mask rasteriser cannot hold a frame of a segmentation's size and modifier over this program (the engine's own
+    rule, moog_engine.hip setup_view / moog_engine_raster_path), or None."""
+    ncopy = 9 if seg.polymod == _abi.MOOG_POLYMOD_TORUS else 1
+    items, points = int(program.n_slots) * ncopy, int(layout.TOTV) * ncopy
+    if items < 1 or points < 1:
+        return 'the program holds no sprite slot'
+    if items > 256:
+        return ('%d polygons per frame (%d sprite slots%s): the mask rasteriser holds at most 256'
+                % (items, program.n_slots, ' x 9 torus copies' if ncopy > 1 else ''))
+    maxv = max(int(program.slot_vcap[s]) for s in range(program.n_slots))
+    pad_w = (int(seg.width) + 15) & ~15
+    need = min(mask_plan_bytes(items, points, pad_w, int(seg.height), int(seg.height), maxv > 32, compact)
+               for compact in (False, True))
+    if need > 64 * 1024:
+        return ('the rasteriser\'s tables for such a frame take %d bytes of LDS, beyond the 64 KB the mask rasteriser plans '
+                'within (%d polygons, %d points)' % (need, items, points))
+    return None
 
 
 def compile_config(state_initializer, physics, task, action_space, observers, game_rules=(),
@@ -1324,14 +1369,25 @@ def compile_config(state_initializer, physics, task, action_space, observers, ga
     obs_items = list(observers.items()) if observers else []
     renderers = [(k, o) for k, o in obs_items if isinstance(o, observers_lib.PILRenderer)]
     others = [o for _, o in obs_items
-              if not isinstance(o, (observers_lib.PILRenderer, observers_lib.RawState, observers_lib.SpriteTable))]
+              if not isinstance(o, (observers_lib.PILRenderer, observers_lib.RawState, observers_lib.SpriteTable,
+                                    observers_lib.Segmentation))]
     if others:
-        raise NotImplementedError('observers other than PILRenderer, RawState and SpriteTable are not lowered (%s)'
+        raise NotImplementedError('observers other than PILRenderer, RawState, SpriteTable and Segmentation are not lowered (%s)'
                                   % (', '.join(sorted(set(type(o).__name__ for o in others))),))
     table_items = [(k, o) for k, o in obs_items if isinstance(o, observers_lib.SpriteTable)]
     if len(table_items) > _abi.MOOG_MAX_TABLES:
         raise NotImplementedError('at most %d SpriteTable observers per config (MOOG_MAX_TABLES), got %d'
                                   % (_abi.MOOG_MAX_TABLES, len(table_items)))
+    seg_items = [(k, o) for k, o in obs_items if isinstance(o, observers_lib.Segmentation)]
+    if len(seg_items) > _abi.MOOG_MAX_SEGMENTATIONS:
+        raise NotImplementedError('at most %d Segmentation observers per config (MOOG_MAX_SEGMENTATIONS), got %d'
+                                  % (_abi.MOOG_MAX_SEGMENTATIONS, len(seg_items)))
+    if seg_items and not renderers:
+        # (a config without a PILRenderer lowers to a program that draws no frames: its engine has no raster state and takes
+        #  no views; a Segmentation there is refused for now, not ruled out -- DESIGN 8)
+        raise NotImplementedError('Segmentation observer %r: the config has no PILRenderer -- its engine draws no frames and '
+                                  'holds no raster state, and masks are drawn on the calls that draw the frames (add a '
+                                  'PILRenderer observer)' % (seg_items[0][0],))
     if len(renderers) > _abi.MOOG_MAX_VIEWS:
         raise NotImplementedError('at most %d PILRenderer observers per config (MOOG_MAX_VIEWS), got %d'
                                   % (_abi.MOOG_MAX_VIEWS, len(renderers)))
@@ -1424,12 +1480,21 @@ def compile_config(state_initializer, physics, task, action_space, observers, ga
                  [(slot_of[id(sp)], key, cell, table) for sp, key, cell, table in getattr(tr, 'dynamic_meta', [])
                   if id(sp) in slot_of],
                  # PILRenderer(color_to_rgb=<a callable>): evaluated on the host (environment.py _refresh_colors)
-                 color_fn, layer_n_init, views, [], {})
+                 color_fn, layer_n_init, views, [], {}, [], {})
     # SpriteTables read the finished layout (rows = the slots of their layers) and leave the program alone
     for key, o in table_items:
         T, rows = o.lower(P, layer_names)
         c.tables.append((key, T))
         c.table_rows[key] = rows
+    # Segmentations read the finished layout too (ids per sprite slot); whether the mask rasteriser can hold such a frame
+    # (moog_engine_raster_path's criteria) is checked here, so that the refusal comes when the config is lowered
+    for key, o in seg_items:
+        G, rows = o.lower(P, layer_names)
+        why = segmentation_refusal(P, c.layout, G)
+        if why:
+            raise NotImplementedError('Segmentation observer %r: %s' % (key, why))
+        c.segmentations.append((key, G))
+        c.segmentation_rows[key] = rows
     # shape id -> Sprite.shape value (sprite.py:517-523): the name, or 'custom' for raw vertices
     c.shape_names.extend(k[1] if k[0] == 'name' else 'custom' for k, _ in shapes.entries)
     return c

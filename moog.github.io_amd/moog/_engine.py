@@ -23,6 +23,7 @@ SYMBOLS = (
     'moog_engine_kernel_variant', 'moog_engine_raster_path', 'moog_engine_read_draw_records', 'moog_program_step_kernel', 'moog_engine_step_kernel',
     'moog_engine_add_view', 'moog_engine_set_view_image', 'moog_engine_view_raster_path',
     'moog_engine_add_table', 'moog_engine_set_table_buffer', 'moog_engine_observe_tables',
+    'moog_engine_add_segmentation', 'moog_engine_set_segmentation_image',
 )
 
 _LIB = None
@@ -81,6 +82,8 @@ def load_library(path=None):
     lib.moog_engine_add_table.argtypes = [vp, ctypes.POINTER(_abi.Table), ctypes.POINTER(i32)]
     lib.moog_engine_set_table_buffer.argtypes = [vp, i32, vp]
     lib.moog_engine_observe_tables.argtypes = [vp, vp]
+    lib.moog_engine_add_segmentation.argtypes = [vp, ctypes.POINTER(_abi.Segmentation), ctypes.POINTER(i32)]
+    lib.moog_engine_set_segmentation_image.argtypes = [vp, i32, vp]
     lib.moog_engine_read_draw_records.argtypes = [vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i32)]
     lib.moog_program_step_kernel.argtypes = [ctypes.POINTER(_abi.Program), ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(u64)]
     lib.moog_engine_step_kernel.argtypes = [vp, ctypes.POINTER(i32)]

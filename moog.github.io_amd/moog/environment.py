@@ -7,7 +7,7 @@ float64[N] (NaN where the reference returns None), discount float64[N],
 observation {'image': uint8[N,H,W,3]} -- all torch tensors on the device; a config with several
 PILRenderers gets one such tensor per renderer key (the engine's extra views), one with none only
 its RawState entries; a SpriteTable observer's entry is its float32 / float16 tensor [N, rows, columns], rewritten in place
-like the frames.
+like the frames, a Segmentation observer's its uint8 id image [N, H, W], drawn with the frames.
 Auto-reset follows environment.py:100-101 per env: the call after a LAST
 timestep ignores that env's action and returns a FIRST timestep.
 
@@ -151,6 +151,7 @@ class BatchedEnvironment(object):
         _engine.check(self._lib, self._lib.moog_engine_load_state(self._handle, ctypes.byref(view)))
         self._attach_views()
         self._attach_tables()
+        self._attach_segmentations()
         self._out = _abi.StepOut()
         self._out.reward = ctypes.cast(self.reward.data_ptr(), ctypes.POINTER(ctypes.c_double))
         self._out.discount = ctypes.cast(self.discount.data_ptr(), ctypes.POINTER(ctypes.c_double))
@@ -221,6 +222,23 @@ class BatchedEnvironment(object):
                 self._handle, idx.value, ctypes.c_void_p(self.view_images[key].data_ptr())))
             self._view_index[key] = idx.value
 
+    def _attach_segmentations(self):
+        """The config's Segmentation observers: a segmentation of the engine each (moog_engine_add_segmentation), drawn into
+        its own tensor (kept beside the extra views' frames, `view_images`) whenever the primary's frames are drawn."""
+        self._segmentation_index = {}
+        for key, seg in self.compiled.segmentations:
+            idx = ctypes.c_int32()
+            with self._torch.cuda.device(self.device):
+                _engine.check(self._lib, self._lib.moog_engine_add_segmentation(self._handle, ctypes.byref(seg), ctypes.byref(idx)))
+            _engine.check(self._lib, self._lib.moog_engine_set_segmentation_image(
+                self._handle, idx.value, ctypes.c_void_p(self.view_images[key].data_ptr())))
+            self._segmentation_index[key] = idx.value
+
+    def segmentation_rows(self, key):
+        """[(layer name, index in layer)] for every row of the Segmentation observer `key`: value v of an 'instance' mask is
+        row v - 1 (the rows of a SpriteTable over the same layers); value v of a 'layer' mask is the v-th chosen layer."""
+        return list(self.compiled.segmentation_rows[key])
+
     def _attach_tables(self):
         """The config's SpriteTables: a sprite table of the engine each (moog_engine_add_table), written into its own tensor
         by every reset / step call and by observation()."""
@@ -257,9 +275,13 @@ class BatchedEnvironment(object):
 
     @staticmethod
     def allocate_view_buffers(torch, compiled, n, device):
-        """{key: uint8 [n, H, W, 3]} for the extra views (the config's PILRenderers after the first)."""
-        return {key: torch.zeros((n, int(R.height), int(R.width), 3), dtype=torch.uint8, device=device)
+        """{key: uint8 [n, H, W, 3]} for the extra views (the config's PILRenderers after the first) and {key: uint8
+        [n, H, W]} for its Segmentation observers."""
+        bufs = {key: torch.zeros((n, int(R.height), int(R.width), 3), dtype=torch.uint8, device=device)
                 for key, R in compiled.views}
+        bufs.update({key: torch.zeros((n, int(G.height), int(G.width)), dtype=torch.uint8, device=device)
+                     for key, G in compiled.segmentations})
+        return bufs
 
     def _setup_color_fn(self):
         """PILRenderer(color_to_rgb=<a callable>): the callable is evaluated here, on the host, once per distinct colour
@@ -631,6 +653,7 @@ class BatchedEnvironment(object):
             self.tables = self.allocate_table_buffers(torch, new_c, self.num_envs, self.device)
             self._attach_tables()
             self._observe_tables()
+            self._attach_segmentations()   # (other capacities, other ids; the tensors keep their size)
             if f32:
                 _engine.check(self._lib, self._lib.moog_engine_set_action_dtype(self._handle, 1))
             self._apply_action_repeat()
@@ -638,6 +661,8 @@ class BatchedEnvironment(object):
             self.enable_cost_schedule(True)
         self._apply_reset_pool()
         self._setup_color_fn()
+        if self.compiled.segmentations:   # (the masks under the new ids at once, like the tables: drawn with the frames)
+            self.observation()
         self.capacity_growths = getattr(self, 'capacity_growths', []) + [dict(caps)]
         if was_specialised and self.step_kernel() != 'specialised' and not getattr(self, '_warned_generic', False):
             self._warned_generic = True
@@ -1172,6 +1197,9 @@ class SubBatchedEnvironment(object):
 
     def table_rows(self, key):
         return self.parts[0].table_rows(key)
+
+    def segmentation_rows(self, key):
+        return self.parts[0].segmentation_rows(key)
 
     def table_columns(self, key):
         return self.parts[0].table_columns(key)

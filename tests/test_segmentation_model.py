@@ -1,0 +1,153 @@
+"""Host model of the segmentation views (tests/csrc/segmentation_model.cpp): the emitter, the mask rasteriser's phases and
+rm_p5_ids (moog.github.io_amd/csrc/moog_raster_mask_core.h) compiled with g++ and run thread by thread, as
+tests/test_raster_mask_model.py runs the frames' kernel.  Ground truth: the `ids_<key>` arrays the reference's own PILRenderer
+drew (tests/golden/make_golden_segmentation.py), every recorded state of every seg_zoo level, every byte; and, on random and
+degenerate polygons under random ids, the coverage masks the RGB compose reads.  No GPU needed."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import helpers
+from moog import _abi, _compiler
+from moog_demos.example_configs import seg_zoo
+from test_raster_mask_model import random_polygon
+
+SRC = os.path.join(helpers.REPO, 'tests', 'csrc', 'segmentation_model.cpp')
+CSRC = os.path.join(helpers.REPO, 'moog.github.io_amd', 'csrc')
+BUILD = os.path.join(helpers.REPO, 'tests', '_build')
+SO = os.path.join(BUILD, 'libsegmentation_model.so')
+_P = ctypes.POINTER
+LEVELS = (0, 1, 2, 3, 4)
+CAPACITY = {4: {'prey': 8, 'predators': 8}}   # (the capacities level 4 was recorded with: the defaults, spelled out)
+
+
+def build_model():
+    os.makedirs(BUILD, exist_ok=True)
+    deps = [SRC, os.path.join(CSRC, 'moog_raster_mask_core.h'), os.path.join(CSRC, 'moog_draw_record.h'),
+            os.path.join(helpers.REPO, 'include', 'moog_engine.h')]
+    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in deps):
+        tmp = SO + '.%d.tmp' % os.getpid()   # (xdist workers may build at the same time)
+        subprocess.check_call(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared', '-Wall',
+                               '-Wno-unused-function', SRC, '-o', tmp])
+        os.replace(tmp, SO)
+    lib = ctypes.CDLL(SO)
+    lib.seg_model_plan_bytes.restype = ctypes.c_longlong
+    return lib
+
+
+@pytest.fixture(scope='module')
+def model():
+    return build_model()
+
+
+def recording(level):
+    with np.load(os.path.join(helpers.GOLDEN, 'seg_zoo_l%d.npz' % level)) as z:
+        return {k: z[k] for k in z.files}
+
+
+def compiled(level):
+    return _compiler.compile_config(layer_capacity=CAPACITY.get(level), **seg_zoo.get_config(level))
+
+
+def model_ids(m, c, G, f64, i32, cap_rows, compact=0):
+    n = f64.shape[0]
+    W, H = (int(G.width) + 15) & ~15, int(G.height)
+    ids = np.full((n, H, W), 0xEE, np.uint8)   # (whatever the buffer held)
+    st = np.zeros(4, np.int64)
+    rc = m.seg_model_frames(ctypes.byref(c.program), ctypes.byref(G), f64.ctypes.data_as(_P(ctypes.c_double)),
+                            i32.ctypes.data_as(_P(ctypes.c_int32)), n, ids.ctypes.data_as(_P(ctypes.c_uint8)), 128, cap_rows,
+                            compact, st.ctypes.data_as(_P(ctypes.c_longlong)))
+    assert rc == 0, rc
+    return ids[:, :, :int(G.width)], int(st[0])
+
+
+@pytest.mark.parametrize('level', LEVELS)
+def test_model_ids_equal_the_references(model, level):
+    """Every recorded state of the level through the emitter, the phases and rm_p5_ids -- row records unlimited and as few as
+    a plan may have (several passes per frame), 16-byte and 4-byte edge records -- equals what the reference's PILRenderer
+    drew, in every byte of every call."""
+    c, fx = compiled(level), recording(level)
+    P, L = c.program, c.layout
+    T = len(fx['step_type'])
+    f64 = np.zeros((T, L.f64_per_env))
+    i32 = np.zeros((T, L.i32_per_env), np.int32)
+    for t in range(T):
+        helpers.records_from_fixture(fx, t, c, f64, i32, env=t)
+    assert c.segmentations and set(k for k, _ in c.segmentations) == set(seg_zoo.segmentations(level))
+    for key, G in c.segmentations:
+        ref = fx['ids_' + key]
+        assert ref.shape == (T, G.height, G.width) and ref.dtype == np.uint8 and ref.any()
+        ncopy = 9 if G.polymod == _abi.MOOG_POLYMOD_TORUS else 1
+        unlimited = min(4096, int(P.n_slots) * ncopy * int(G.height))
+        passes = {}
+        for cap_rows in (unlimited, 192, int(G.height)):
+            for compact in (0, 1):
+                ids, passes[cap_rows] = model_ids(model, c, G, f64, i32, cap_rows, compact)
+                bad = np.nonzero((ids != ref).reshape(T, -1).any(axis=1))[0]
+                assert bad.size == 0, ('calls whose mask differs from the reference\'s (cap_rows %d, compact %d)' % (cap_rows, compact),
+                                       key, bad[:8].tolist(), int(bad.size), int((ids[bad[0]] != ref[bad[0]]).sum()))
+        print('seg_zoo_l%d %s: %d masks of %d x %d equal; passes %s' % (level, key, T, G.width, G.height, passes))
+        if level == 3:   # (more rows than the engine's 192 records: several passes, later ones on top of the image)
+            assert passes[192] > T and max(int(P.slot_vcap[s]) for s in range(P.n_slots)) > 32
+
+
+def test_recordings_hold_what_the_levels_are_for():
+    """The cases the levels exist for are in the recorded masks: a translucent owner, an opacity-0 sprite that owns nothing,
+    unchosen layers that occlude to 0, ids on both sides of a torus frame, a first-person frame, packed dynamic slots."""
+    fx = recording(0)
+    c = compiled(0)
+    rows = c.segmentation_rows['seg']
+    back = [1 + rows.index(('back', k)) for k in range(4)]
+    seg, lay = fx['ids_seg'], fx['ids_seg_layer']
+    assert (seg == back[1]).any(), 'the translucent square owns pixels'
+    assert not (seg == back[2]).any(), 'the square of opacity 0 owns none'
+    assert (seg == back[3]).any() and set(np.unique(lay)) == {0, 1, 2}
+    assert ((lay == 0) & np.isin(seg, back)).any() and not ((lay != 0) & np.isin(seg, back)).any()
+    fx = recording(1)
+    edge0 = fx['ids_seg'][0] == 1   # the square on the left edge: its copy shows on the right
+    assert edge0[:, :4].any() and edge0[:, -4:].any()
+    fx, c = recording(4), compiled(4)
+    assert fx['ids_seg'].max() > 9   # (rows: 8 prey slots, the agent, 8 predator slots)
+
+
+@pytest.mark.parametrize('seed', [0, 1])
+def test_ids_compose_equals_last_covering_item(model, seed):
+    """5000 random and degenerate polygons per seed (the families of test_raster_mask_model), eight to a frame under random
+    ids and opacities (a quarter of them 0): rm_p5_ids equals the last polygon with opacity != 0 whose coverage mask -- the
+    row masks the RGB compose reads -- has the pixel's bit; with few row records, so that frames take several passes."""
+    rs = np.random.RandomState(977 + seed)
+    covered = multi = 0
+    for frame in range(625):
+        W = int(rs.choice([16, 48, 64, 64, 80, 128]))
+        polys = [random_polygon(rs, W, int(rs.randint(10))) for _ in range(8)]
+        nv = np.array([len(p) for p in polys], np.int32)
+        xy = np.ascontiguousarray(np.concatenate(polys), np.int32)
+        ids = rs.randint(0, 256, size=8).astype(np.uint8)
+        alpha = rs.choice([0, 1, 128, 255], size=8).astype(np.uint8)
+        got, want = np.empty((W, W), np.uint8), np.empty((W, W), np.uint8)
+        cap_rows = W if frame % 2 else 4096
+        passes = model.seg_model_polygons(xy.ctypes.data_as(_P(ctypes.c_int)), nv.ctypes.data_as(_P(ctypes.c_int)),
+                                          ids.ctypes.data_as(_P(ctypes.c_uint8)), alpha.ctypes.data_as(_P(ctypes.c_uint8)), 8, W, W,
+                                          cap_rows, frame % 3 == 0, got.ctypes.data_as(_P(ctypes.c_uint8)),
+                                          want.ctypes.data_as(_P(ctypes.c_uint8)))
+        assert passes >= 1, passes
+        assert np.array_equal(got, want), (frame, W, int((got != want).sum()), [p.tolist() for p in polys], ids.tolist(), alpha.tolist())
+        covered += int((want != 0).sum())
+        multi += passes > 1
+    assert covered > 100000 and multi > 50, (covered, multi)
+
+
+def test_plan_restated_in_python(model):
+    """moog._compiler.mask_plan_bytes (the refusal of frames the mask rasteriser cannot hold) against rm_plan itself."""
+    rs = np.random.RandomState(5)
+    for _ in range(400):
+        items, points = int(rs.randint(1, 257)), int(rs.randint(1, 20000))
+        W, H = 16 * int(rs.randint(1, 9)), int(rs.randint(1, 129))
+        cap = int(rs.randint(H, 4097))
+        for big in (0, 1):
+            for compact in (0, 1):
+                assert _compiler.mask_plan_bytes(items, points, W, H, cap, bool(big), bool(compact)) == \
+                    model.seg_model_plan_bytes(items, points, W, H, cap, big, compact)
