@@ -54,6 +54,8 @@ extern "C" {
 #define MOOG_MAX_TABLES 4    /* SpriteTable observers one engine writes (moog_engine_add_table) */
 #define MOOG_MAX_SEGMENTATIONS 2   /* Segmentation observers one engine draws (moog_engine_add_segmentation) */
 #define MOOG_MAX_TABLE_COLS 17 /* columns of one table: MOOG_TCOL_COUNT */
+#define MOOG_MAX_SENSORS 4   /* RaySensor observers one engine casts (moog_engine_add_sensor) */
+#define MOOG_MAX_RAYS 256    /* rays of one sensor */
 #define MOOG_MAX_HDRAWS 32   /* draws a state_initializer takes from np.random directly (per reset) */
 #define MOOG_MAX_OP_DRAWS 24 /* draws of one generation op: its sampled factors + the direct draws made between them */
 
@@ -726,6 +728,26 @@ typedef struct {
   int32_t row_slot[MOOG_MAX_SLOTS];
 } moog_table_t;
 
+/* A ray sensor (the RaySensor observer): one dense [n_envs][n_rays][2] tensor of egocentric range readings, cast on the device
+ * over the state records' world vertices.  Channel 0 of a ray is the distance to the nearest hit, channel 1 what was hit: in
+ * MOOG_SENSOR_INSTANCE mode 1 + the row (the rows of a moog_table_t over the same slots), in MOOG_SENSOR_LAYER mode 1 + the
+ * position of the row's layer among the rows' layers (rows come layer after layer), 0 for no hit.  csrc/moog_ray_sensor.h
+ * states the arithmetic. */
+#define MOOG_SENSOR_FOLLOW_ANGLE 1   /* flags: the device rotates the directions by the origin sprite's angle */
+#define MOOG_SENSOR_VISIBLE_ONLY 2   /* flags: a slot with opacity <= 0 is no target */
+enum { MOOG_SENSOR_INSTANCE = 0, MOOG_SENSOR_LAYER = 1 };
+typedef struct {
+  int32_t n_rows;        /* 1 .. MOOG_MAX_SLOTS (at most 255 in MOOG_SENSOR_INSTANCE mode: an id is 1 .. 255) */
+  int32_t n_rays;        /* 1 .. MOOG_MAX_RAYS */
+  int32_t origin_slot;   /* the sprite slot the rays start from (its `position`); never a target */
+  int32_t flags;         /* MOOG_SENSOR_FOLLOW_ANGLE | MOOG_SENSOR_VISIBLE_ONLY */
+  int32_t mode;          /* MOOG_SENSOR_INSTANCE / MOOG_SENSOR_LAYER */
+  int32_t dtype;         /* MOOG_TABLE_F32 / MOOG_TABLE_F16 */
+  double max_range;      /* finite, > 0, at most 65504 for MOOG_TABLE_F16; the reading of a ray that hits nothing */
+  int32_t row_slot[MOOG_MAX_SLOTS];
+  double dirs[MOOG_MAX_RAYS][2];   /* unit vectors in arena coordinates, computed by the caller; all finite */
+} moog_sensor_t;
+
 /* A segmentation (the Segmentation observer): one [n_envs][height][width] uint8 image of sprite ids, drawn on the device like
  * a view's frame.  slot_id[s] is what a pixel shows when sprite slot s is the last-drawn sprite with opacity > 0 that covers
  * it (0: the slot occludes and shows as background).  The modifier fields are moog_render_t's. */
@@ -738,7 +760,8 @@ typedef struct {
 } moog_segmentation_t;
 
 /* kernel ids for moog_engine_kernel_time() */
-/* MOOG_K_TABLES: the one launch that writes a call's sprite tables (moog_engine_add_table). */
+/* MOOG_K_TABLES: the one launch that writes a call's sprite tables (moog_engine_add_table) and the one that casts its ray
+ * sensors (moog_engine_add_sensor): one bracket per call around both. */
 /* MOOG_K_RASTER: the program's own frames (views[0]); MOOG_K_VIEWS: everything the extra views of moog_engine_add_view cost a
  * call -- their one derive launch (which also derives the primary's records when a render call needs them) and their raster,
  * crop and resize launches; the segmentations of moog_engine_add_segmentation are timed under MOOG_K_VIEWS too, one bracket
@@ -829,6 +852,26 @@ int moog_engine_view_raster_path(moog_engine_t* e, int32_t view, int32_t* path);
 int moog_engine_add_table(moog_engine_t* e, const moog_table_t* table_desc, int32_t* table);
 int moog_engine_set_table_buffer(moog_engine_t* e, int32_t table, void* table_dev);
 int moog_engine_observe_tables(moog_engine_t* e, void* hip_stream);
+
+/* Ray sensors.  Egocentric range readings for a state-based agent: how far, and to what, along each of n_rays directions from
+ * one sprite.  The reference has no such observer (it leaves featurising to the caller, observers/raw_state.py:17-19).
+ * moog_engine_add_sensor adds one to the engine and returns its index (0 .. MOOG_MAX_SENSORS - 1) in *sensor.  Like tables,
+ * sensors belong to the engine handle, never to the program: its bytes, its hash and the step, reset and raster kernels do not
+ * know about them.
+ * MOOG_E_INVALID: n_rays outside 1 .. MOOG_MAX_RAYS, n_rows outside 1 .. MOOG_MAX_SLOTS or above 255 in instance mode, a row's
+ * slot or the origin slot outside 0 .. n_slots - 1, a slot named by two rows, an unknown mode or dtype, unknown flag bits,
+ * max_range not finite, <= 0, or above 65504 with MOOG_TABLE_F16 (the no-hit reading would become inf), a direction that is
+ * not finite, or a sensor beyond MOOG_MAX_SENSORS.
+ * moog_engine_set_sensor_buffer binds the device buffer [n_envs][n_rays][2] of the sensor's dtype (borrowed; 4-byte aligned
+ * for both dtypes: a float16 ray is one dword; NULL unbinds).
+ * moog_engine_reset and moog_engine_step cast every bound sensor themselves, in ONE launch for all of them, behind the
+ * tables' launch: the readings are those of the records as the call left them.  An engine without a bound sensor launches
+ * nothing; one without a bound table or sensor pays one comparison.  moog_engine_observe_sensors is that launch on its own.
+ * Limits: no torus wrap-around and no polygon modifier (rays run in arena coordinates over the records' vertices);
+ * moog_engine_physics_only and moog_engine_render cast no sensors. */
+int moog_engine_add_sensor(moog_engine_t* e, const moog_sensor_t* sensor_desc, int32_t* sensor);
+int moog_engine_set_sensor_buffer(moog_engine_t* e, int32_t sensor, void* sensor_dev);
+int moog_engine_observe_sensors(moog_engine_t* e, void* hip_stream);
 
 /* Segmentations.  Ground-truth instance masks of the frame an agent sees: per pixel the id of the sprite visible there.  The
  * reference has no such observer; what it would draw is defined through its renderer -- pil_renderer.py:100-118 with every

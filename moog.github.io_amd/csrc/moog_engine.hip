@@ -21,6 +21,7 @@
 
 #include "moog_raster.h"
 #include "moog_sprite_table.h"
+#include "moog_ray_sensor.h"
 #include <dlfcn.h>
 #include <unistd.h>
 
@@ -91,6 +92,14 @@ struct SegView {
   uint8_t* pad_ids = nullptr;  // [n_envs][height][pad_w] when the width is no multiple of 16 (cropped into `ids`)
 };
 
+// A ray sensor of the engine (moog_engine_add_sensor): the kernel's descriptor, its rows and directions on the device, and -- in
+// desc.out -- the bound buffer (moog_engine_set_sensor_buffer), or null.
+struct SSensor {
+  RsSensor desc{};
+  int32_t* d_rows = nullptr;
+  double* d_dirs = nullptr;
+};
+
 struct moog_engine {
   moog_program_t prog;
   moog_layout_t L;
@@ -120,6 +129,8 @@ struct moog_engine {
   int n_views = 1;               // views[0] and the extra views added so far
   STable tables[MOOG_MAX_TABLES];
   int n_tables = 0, n_bound_tables = 0;   // tables added so far; how many of them have a buffer
+  SSensor sensors[MOOG_MAX_SENSORS];
+  int n_sensors = 0, n_bound_sensors = 0;   // the same for ray sensors
   SegView segs[MOOG_MAX_SEGMENTATIONS];
   int n_segs = 0, n_bound_segs = 0;       // segmentations added so far; how many of them have an image
   bool frameless = false;        // render 0 x 0: the program draws no frames (no raster state at all)
@@ -182,6 +193,10 @@ static void free_engine(moog_engine* e) {
     if (v.rows_seen) hipHostFree(v.rows_seen);
   }
   for (STable& t : e->tables) if (t.d_rows) hipFree(t.d_rows);
+  for (SSensor& t : e->sensors) {
+    if (t.d_rows) hipFree(t.d_rows);
+    if (t.d_dirs) hipFree(t.d_dirs);
+  }
   for (SegView& g : e->segs) {
     if (g.v.draw) hipFree(g.v.draw);
     if (g.v.rows_seen) hipHostFree(g.v.rows_seen);
@@ -1171,20 +1186,33 @@ static int launch_frames(moog_engine* e, uint8_t* image, hipStream_t s, bool dra
   return launch_raster(e, p, image, s, draw_ready || join);
 }
 
-// Every bound sprite table of the engine from the records as they are on stream s: one launch (moog_sprite_table.h).  An
-// engine without a bound table returns at the first comparison.
-static int launch_tables(moog_engine* e, hipStream_t s) {
-  if (e->n_bound_tables == 0) return MOOG_OK;
-  StArgs a;
-  a.f64 = e->view.f64; a.i32 = e->view.i32;
-  a.f64_per_env = e->L.f64_per_env; a.i32_per_env = e->L.i32_per_env;
-  a.n_envs = e->n_envs; a.chunk_envs = 0; a.o_flags = e->L.o_flags; a.n_tables = 0;
-  for (int k = 0; k < e->n_tables; ++k)
-    if (e->tables[k].desc.out) a.t[a.n_tables++] = e->tables[k].desc;
-  for (int k = a.n_tables; k < MOOG_MAX_TABLES; ++k) memset(&a.t[k], 0, sizeof a.t[k]);
+// Every bound sprite table and every bound ray sensor of the engine from the records as they are on stream s: one launch for
+// the tables (moog_sprite_table.h), one for the sensors (moog_ray_sensor.h), inside one MOOG_K_TABLES bracket.  An engine
+// without either returns at the first comparison.
+enum { OBSERVE_TABLES = 1, OBSERVE_SENSORS = 2 };
+static int launch_tables(moog_engine* e, hipStream_t s, int what = OBSERVE_TABLES | OBSERVE_SENSORS) {
+  if (e->n_bound_tables + e->n_bound_sensors == 0) return MOOG_OK;
+  const bool tables = (what & OBSERVE_TABLES) && e->n_bound_tables, sensors = (what & OBSERVE_SENSORS) && e->n_bound_sensors;
+  if (!tables && !sensors) return MOOG_OK;
   {
     Bracket br(e, MOOG_K_TABLES, s);
-    moog_sprite_table_launch(a, s);
+    if (tables) {
+      StArgs a;
+      a.f64 = e->view.f64; a.i32 = e->view.i32;
+      a.f64_per_env = e->L.f64_per_env; a.i32_per_env = e->L.i32_per_env;
+      a.n_envs = e->n_envs; a.chunk_envs = 0; a.o_flags = e->L.o_flags; a.n_tables = 0;
+      for (int k = 0; k < e->n_tables; ++k)
+        if (e->tables[k].desc.out) a.t[a.n_tables++] = e->tables[k].desc;
+      for (int k = a.n_tables; k < MOOG_MAX_TABLES; ++k) memset(&a.t[k], 0, sizeof a.t[k]);
+      moog_sprite_table_launch(a, s);
+    }
+    if (sensors) {
+      RsArgs a;
+      moog_rs_args(&e->L, e->view.f64, e->view.i32, e->n_envs, &a);
+      for (int k = 0; k < e->n_sensors; ++k)
+        if (e->sensors[k].desc.out) a.s[a.n_sensors++] = e->sensors[k].desc;
+      moog_ray_sensor_launch(a, s);
+    }
   }
   HIPCHK(hipGetLastError());
   return MOOG_OK;
@@ -1613,7 +1641,45 @@ int moog_engine_set_table_buffer(moog_engine_t* e, int32_t table, void* table_de
 int moog_engine_observe_tables(moog_engine_t* e, void* hip_stream) {
   const int rc = ready(e);
   if (rc) return rc;
-  return launch_tables(e, (hipStream_t)hip_stream);
+  return launch_tables(e, (hipStream_t)hip_stream, OBSERVE_TABLES);
+}
+
+int moog_engine_add_sensor(moog_engine_t* e, const moog_sensor_t* sensor_desc, int32_t* sensor) {
+  if (!e || !sensor_desc || !sensor) return fail(MOOG_E_INVALID, "null argument");
+  if (e->n_sensors >= MOOG_MAX_SENSORS) return fail(MOOG_E_INVALID, "at most MOOG_MAX_SENSORS ray sensors per engine");
+  SSensor& t = e->sensors[e->n_sensors];
+  int32_t rows[3 * MOOG_MAX_SLOTS];
+  RsSensor d;
+  memset(&d, 0, sizeof d);
+  const char* why = moog_rs_describe(&e->prog, &e->L, sensor_desc, &d, rows);
+  if (why) return fail(MOOG_E_INVALID, why);
+  const size_t rows_bytes = sizeof(int32_t) * 3 * (size_t)sensor_desc->n_rows, dirs_bytes = sizeof(double) * 2 * (size_t)sensor_desc->n_rays;
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipMalloc(&t.d_rows, rows_bytes));
+  HIPCHK(hipMemcpy(t.d_rows, rows, rows_bytes, hipMemcpyHostToDevice));
+  HIPCHK(hipMalloc(&t.d_dirs, dirs_bytes));
+  HIPCHK(hipMemcpy(t.d_dirs, sensor_desc->dirs, dirs_bytes, hipMemcpyHostToDevice));
+  d.rows = t.d_rows;
+  d.dirs = t.d_dirs;
+  t.desc = d;
+  *sensor = e->n_sensors++;
+  return MOOG_OK;
+}
+
+int moog_engine_set_sensor_buffer(moog_engine_t* e, int32_t sensor, void* sensor_dev) {
+  if (!e) return fail(MOOG_E_INVALID, "null engine");
+  if (sensor < 0 || sensor >= e->n_sensors) return fail(MOOG_E_INVALID, "no such ray sensor");
+  RsSensor& d = e->sensors[sensor].desc;
+  if ((uintptr_t)sensor_dev & 3u) return fail(MOOG_E_INVALID, "ray sensor buffer must be 4-byte aligned (a float16 ray is one dword)");
+  e->n_bound_sensors += (sensor_dev ? 1 : 0) - (d.out ? 1 : 0);
+  d.out = sensor_dev;
+  return MOOG_OK;
+}
+
+int moog_engine_observe_sensors(moog_engine_t* e, void* hip_stream) {
+  const int rc = ready(e);
+  if (rc) return rc;
+  return launch_tables(e, (hipStream_t)hip_stream, OBSERVE_SENSORS);
 }
 
 int moog_engine_kernel_variant(moog_engine_t* e, int32_t* variant, int32_t* late_reset) {

@@ -7,7 +7,8 @@ float64[N] (NaN where the reference returns None), discount float64[N],
 observation {'image': uint8[N,H,W,3]} -- all torch tensors on the device; a config with several
 PILRenderers gets one such tensor per renderer key (the engine's extra views), one with none only
 its RawState entries; a SpriteTable observer's entry is its float32 / float16 tensor [N, rows, columns], rewritten in place
-like the frames, a Segmentation observer's its uint8 id image [N, H, W], drawn with the frames.
+like the frames, a Segmentation observer's its uint8 id image [N, H, W], drawn with the frames, a RaySensor observer's its
+float32 / float16 readings [N, rays, 2], kept beside the tables' tensors and rewritten with them.
 Auto-reset follows environment.py:100-101 per env: the call after a LAST
 timestep ignores that env's action and returns a FIRST timestep.
 
@@ -151,6 +152,7 @@ class BatchedEnvironment(object):
         _engine.check(self._lib, self._lib.moog_engine_load_state(self._handle, ctypes.byref(view)))
         self._attach_views()
         self._attach_tables()
+        self._attach_sensors()
         self._attach_segmentations()
         self._out = _abi.StepOut()
         self._out.reward = ctypes.cast(self.reward.data_ptr(), ctypes.POINTER(ctypes.c_double))
@@ -251,17 +253,48 @@ class BatchedEnvironment(object):
                 self._handle, idx.value, ctypes.c_void_p(self.tables[key].data_ptr())))
             self._table_index[key] = idx.value
 
+    def _attach_sensors(self):
+        """The config's RaySensors: a ray sensor of the engine each (moog_engine_add_sensor), cast into its own tensor (kept
+        beside the tables' tensors, `tables`) by every reset / step call and by observation()."""
+        self._sensor_index = {}
+        for key, sensor in self.compiled.sensors:
+            idx = ctypes.c_int32()
+            with self._torch.cuda.device(self.device):
+                _engine.check(self._lib, self._lib.moog_engine_add_sensor(self._handle, ctypes.byref(sensor), ctypes.byref(idx)))
+            _engine.check(self._lib, self._lib.moog_engine_set_sensor_buffer(
+                self._handle, idx.value, ctypes.c_void_p(self.tables[key].data_ptr())))
+            self._sensor_index[key] = idx.value
+
+    def ray_rows(self, key):
+        """[(layer name, index in layer)] for every row of the RaySensor observer `key`: id v of an 'instance' sensor is row
+        v - 1 (the rows of a SpriteTable over the same layers); id v of a 'layer' sensor is the v-th chosen layer; 0 is no
+        hit."""
+        return list(self.compiled.sensor_rows[key])
+
+    def ray_directions(self, key):
+        """The [num_rays, 2] float64 unit vectors the engine was given for the RaySensor observer `key`."""
+        T = dict(self.compiled.sensors)[key]
+        return np.array([[T.dirs[k][0], T.dirs[k][1]] for k in range(int(T.n_rays))], dtype=np.float64)
+
     def _observe_tables(self):
         if self.compiled.tables:
             with self._torch.cuda.device(self.device):
                 _engine.check(self._lib, self._lib.moog_engine_observe_tables(self._handle, self._stream()))
+        if self.compiled.sensors:
+            with self._torch.cuda.device(self.device):
+                _engine.check(self._lib, self._lib.moog_engine_observe_sensors(self._handle, self._stream()))
 
     @staticmethod
     def allocate_table_buffers(torch, compiled, n, device):
-        """{key: float32 / float16 [n, rows, columns]} for the config's SpriteTables."""
-        return {key: torch.zeros((n, int(T.n_rows), int(T.n_cols)), device=device,
+        """{key: float32 / float16 [n, rows, columns]} for the config's SpriteTables and {key: float32 / float16
+        [n, rays, 2]} for its RaySensors."""
+        bufs = {key: torch.zeros((n, int(T.n_rows), int(T.n_cols)), device=device,
                                  dtype=torch.float16 if T.dtype == _abi.MOOG_TABLE_F16 else torch.float32)
                 for key, T in compiled.tables}
+        bufs.update({key: torch.zeros((n, int(T.n_rays), 2), device=device,
+                                      dtype=torch.float16 if T.dtype == _abi.MOOG_TABLE_F16 else torch.float32)
+                     for key, T in compiled.sensors})
+        return bufs
 
     def table_rows(self, key):
         """[(layer name, index in layer)] for every row of the SpriteTable observer `key`."""
@@ -652,6 +685,7 @@ class BatchedEnvironment(object):
             # (other capacities, other row counts: new tensors, filled from the records that have just moved over)
             self.tables = self.allocate_table_buffers(torch, new_c, self.num_envs, self.device)
             self._attach_tables()
+            self._attach_sensors()   # (other capacities, other rows and ids; the readings under them at once)
             self._observe_tables()
             self._attach_segmentations()   # (other capacities, other ids; the tensors keep their size)
             if f32:
@@ -1200,6 +1234,12 @@ class SubBatchedEnvironment(object):
 
     def segmentation_rows(self, key):
         return self.parts[0].segmentation_rows(key)
+
+    def ray_rows(self, key):
+        return self.parts[0].ray_rows(key)
+
+    def ray_directions(self, key):
+        return self.parts[0].ray_directions(key)
 
     def table_columns(self, key):
         return self.parts[0].table_columns(key)
