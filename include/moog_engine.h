@@ -56,6 +56,7 @@ extern "C" {
 #define MOOG_MAX_TABLE_COLS 17 /* columns of one table: MOOG_TCOL_COUNT */
 #define MOOG_MAX_SENSORS 4   /* RaySensor observers one engine casts (moog_engine_add_sensor) */
 #define MOOG_MAX_RAYS 256    /* rays of one sensor */
+#define MOOG_MAX_CONTACTS 4  /* Contacts observers one engine evaluates (moog_engine_add_contacts) */
 #define MOOG_MAX_HDRAWS 32   /* draws a state_initializer takes from np.random directly (per reset) */
 #define MOOG_MAX_OP_DRAWS 24 /* draws of one generation op: its sampled factors + the direct draws made between them */
 
@@ -748,6 +749,24 @@ typedef struct {
   double dirs[MOOG_MAX_RAYS][2];   /* unit vectors in arena coordinates, computed by the caller; all finite */
 } moog_sensor_t;
 
+/* A contacts observer (the Contacts observer): one dense uint8 tensor of overlap flags between two lists of sprite slots,
+ * evaluated on the device over the state records.  MOOG_CONTACTS_PAIR: [n_envs][n_rows_0][n_rows_1]; entry [i][j] is 1 iff
+ * the slots of row i of the first list and of row j of the second are both alive, are different slots, both have opacity > 0
+ * when MOOG_CONTACTS_VISIBLE_ONLY is set, and sprite.py:462-484 overlaps_sprite holds for the ORDERED pair (row i is `self`).
+ * MOOG_CONTACTS_LAYER: [n_envs][n_rows_0][n_layers_1]; entry [i][l] is 1 iff row i overlaps, by the same rule, any row of
+ * the l-th layer of the second list (its rows come layer after layer; a layer is a run of rows whose slots share
+ * slot_layer).  The two lists may be the same list.  csrc/moog_contacts.h states the predicate. */
+#define MOOG_CONTACTS_VISIBLE_ONLY 1   /* flags: a slot with opacity <= 0 touches nothing */
+enum { MOOG_CONTACTS_PAIR = 0, MOOG_CONTACTS_LAYER = 1 };
+typedef struct {
+  int32_t n_rows_0;      /* 1 .. MOOG_MAX_SLOTS */
+  int32_t n_rows_1;      /* 1 .. MOOG_MAX_SLOTS */
+  int32_t flags;         /* MOOG_CONTACTS_VISIBLE_ONLY */
+  int32_t mode;          /* MOOG_CONTACTS_PAIR / MOOG_CONTACTS_LAYER */
+  int32_t row_slot_0[MOOG_MAX_SLOTS];
+  int32_t row_slot_1[MOOG_MAX_SLOTS];
+} moog_contacts_t;
+
 /* A segmentation (the Segmentation observer): one [n_envs][height][width] uint8 image of sprite ids, drawn on the device like
  * a view's frame.  slot_id[s] is what a pixel shows when sprite slot s is the last-drawn sprite with opacity > 0 that covers
  * it (0: the slot occludes and shows as background).  The modifier fields are moog_render_t's. */
@@ -760,8 +779,9 @@ typedef struct {
 } moog_segmentation_t;
 
 /* kernel ids for moog_engine_kernel_time() */
-/* MOOG_K_TABLES: the one launch that writes a call's sprite tables (moog_engine_add_table) and the one that casts its ray
- * sensors (moog_engine_add_sensor): one bracket per call around both. */
+/* MOOG_K_TABLES: the one launch that writes a call's sprite tables (moog_engine_add_table), the one that casts its ray
+ * sensors (moog_engine_add_sensor) and the one that evaluates its contacts observers (moog_engine_add_contacts): one bracket
+ * per call around all three. */
 /* MOOG_K_RASTER: the program's own frames (views[0]); MOOG_K_VIEWS: everything the extra views of moog_engine_add_view cost a
  * call -- their one derive launch (which also derives the primary's records when a render call needs them) and their raster,
  * crop and resize launches; the segmentations of moog_engine_add_segmentation are timed under MOOG_K_VIEWS too, one bracket
@@ -872,6 +892,25 @@ int moog_engine_observe_tables(moog_engine_t* e, void* hip_stream);
 int moog_engine_add_sensor(moog_engine_t* e, const moog_sensor_t* sensor_desc, int32_t* sensor);
 int moog_engine_set_sensor_buffer(moog_engine_t* e, int32_t sensor, void* sensor_dev);
 int moog_engine_observe_sensors(moog_engine_t* e, void* hip_stream);
+
+/* Contacts.  Who is touching whom: the predicate the step kernel evaluates for ContactReward, contact_rules and the
+ * collision search (sprite.py:462-484 overlaps_sprite: the bounding-circle test, then matplotlib's
+ * Path.intersects_path(filled=True)), made visible for a chosen set of ordered pairs.  The reference has no such observer.
+ * moog_engine_add_contacts adds one to the engine and returns its index (0 .. MOOG_MAX_CONTACTS - 1) in *contacts.  Like
+ * tables and sensors, contacts observers belong to the engine handle, never to the program: its bytes, its hash and the step,
+ * reset and raster kernels do not know about them.
+ * MOOG_E_INVALID: n_rows_0 or n_rows_1 outside 1 .. MOOG_MAX_SLOTS, a row's slot outside 0 .. n_slots - 1, a slot named by two
+ * rows of one list, an unknown mode, unknown flag bits, or an observer beyond MOOG_MAX_CONTACTS.
+ * moog_engine_set_contacts_buffer binds the device buffer, uint8 [n_envs][n_rows_0][n_rows_1] (pair mode) or
+ * [n_envs][n_rows_0][n_layers_1] (layer mode) (borrowed; any byte alignment; NULL unbinds).
+ * moog_engine_reset and moog_engine_step evaluate every bound contacts observer themselves, in ONE launch for all of them,
+ * behind the sensors' launch and inside the same MOOG_K_TABLES bracket: the flags are those of the records as the call left
+ * them.  An engine without a bound one launches nothing.  moog_engine_observe_contacts is that launch on its own.
+ * Limits: no torus wrap-around and no polygon modifier (arena coordinates over the records' vertices); a vertex count above
+ * the slot's capacity is cut to the capacity; moog_engine_physics_only and moog_engine_render evaluate no contacts. */
+int moog_engine_add_contacts(moog_engine_t* e, const moog_contacts_t* contacts_desc, int32_t* contacts);
+int moog_engine_set_contacts_buffer(moog_engine_t* e, int32_t contacts, void* contacts_dev);
+int moog_engine_observe_contacts(moog_engine_t* e, void* hip_stream);
 
 /* Segmentations.  Ground-truth instance masks of the frame an agent sees: per pixel the id of the sprite visible there.  The
  * reference has no such observer; what it would draw is defined through its renderer -- pil_renderer.py:100-118 with every

@@ -22,6 +22,7 @@
 #include "moog_raster.h"
 #include "moog_sprite_table.h"
 #include "moog_ray_sensor.h"
+#include "moog_contacts.h"
 #include <dlfcn.h>
 #include <unistd.h>
 
@@ -100,6 +101,13 @@ struct SSensor {
   double* d_dirs = nullptr;
 };
 
+// A contacts observer of the engine (moog_engine_add_contacts): the kernel's descriptor, its rows on the device, and -- in
+// desc.out -- the bound buffer (moog_engine_set_contacts_buffer), or null.
+struct SContacts {
+  CtObs desc{};
+  int32_t* d_rows = nullptr;
+};
+
 struct moog_engine {
   moog_program_t prog;
   moog_layout_t L;
@@ -131,6 +139,8 @@ struct moog_engine {
   int n_tables = 0, n_bound_tables = 0;   // tables added so far; how many of them have a buffer
   SSensor sensors[MOOG_MAX_SENSORS];
   int n_sensors = 0, n_bound_sensors = 0;   // the same for ray sensors
+  SContacts contacts[MOOG_MAX_CONTACTS];
+  int n_contacts = 0, n_bound_contacts = 0;   // and for contacts observers
   SegView segs[MOOG_MAX_SEGMENTATIONS];
   int n_segs = 0, n_bound_segs = 0;       // segmentations added so far; how many of them have an image
   bool frameless = false;        // render 0 x 0: the program draws no frames (no raster state at all)
@@ -197,6 +207,7 @@ static void free_engine(moog_engine* e) {
     if (t.d_rows) hipFree(t.d_rows);
     if (t.d_dirs) hipFree(t.d_dirs);
   }
+  for (SContacts& t : e->contacts) if (t.d_rows) hipFree(t.d_rows);
   for (SegView& g : e->segs) {
     if (g.v.draw) hipFree(g.v.draw);
     if (g.v.rows_seen) hipHostFree(g.v.rows_seen);
@@ -1186,14 +1197,15 @@ static int launch_frames(moog_engine* e, uint8_t* image, hipStream_t s, bool dra
   return launch_raster(e, p, image, s, draw_ready || join);
 }
 
-// Every bound sprite table and every bound ray sensor of the engine from the records as they are on stream s: one launch for
-// the tables (moog_sprite_table.h), one for the sensors (moog_ray_sensor.h), inside one MOOG_K_TABLES bracket.  An engine
-// without either returns at the first comparison.
-enum { OBSERVE_TABLES = 1, OBSERVE_SENSORS = 2 };
-static int launch_tables(moog_engine* e, hipStream_t s, int what = OBSERVE_TABLES | OBSERVE_SENSORS) {
-  if (e->n_bound_tables + e->n_bound_sensors == 0) return MOOG_OK;
+// Every bound sprite table, ray sensor and contacts observer of the engine from the records as they are on stream s: one
+// launch for the tables (moog_sprite_table.h), one for the sensors (moog_ray_sensor.h), one for the contacts
+// (moog_contacts.h), inside one MOOG_K_TABLES bracket.  An engine without any returns at the first comparison.
+enum { OBSERVE_TABLES = 1, OBSERVE_SENSORS = 2, OBSERVE_CONTACTS = 4 };
+static int launch_tables(moog_engine* e, hipStream_t s, int what = OBSERVE_TABLES | OBSERVE_SENSORS | OBSERVE_CONTACTS) {
+  if (e->n_bound_tables + e->n_bound_sensors + e->n_bound_contacts == 0) return MOOG_OK;
   const bool tables = (what & OBSERVE_TABLES) && e->n_bound_tables, sensors = (what & OBSERVE_SENSORS) && e->n_bound_sensors;
-  if (!tables && !sensors) return MOOG_OK;
+  const bool contacts = (what & OBSERVE_CONTACTS) && e->n_bound_contacts;
+  if (!tables && !sensors && !contacts) return MOOG_OK;
   {
     Bracket br(e, MOOG_K_TABLES, s);
     if (tables) {
@@ -1212,6 +1224,13 @@ static int launch_tables(moog_engine* e, hipStream_t s, int what = OBSERVE_TABLE
       for (int k = 0; k < e->n_sensors; ++k)
         if (e->sensors[k].desc.out) a.s[a.n_sensors++] = e->sensors[k].desc;
       moog_ray_sensor_launch(a, s);
+    }
+    if (contacts) {
+      CtArgs a;
+      moog_ct_args(&e->L, e->view.f64, e->view.i32, e->n_envs, &a);
+      for (int k = 0; k < e->n_contacts; ++k)
+        if (e->contacts[k].desc.out) a.c[a.n_obs++] = e->contacts[k].desc;
+      moog_contacts_launch(a, s);
     }
   }
   HIPCHK(hipGetLastError());
@@ -1680,6 +1699,40 @@ int moog_engine_observe_sensors(moog_engine_t* e, void* hip_stream) {
   const int rc = ready(e);
   if (rc) return rc;
   return launch_tables(e, (hipStream_t)hip_stream, OBSERVE_SENSORS);
+}
+
+int moog_engine_add_contacts(moog_engine_t* e, const moog_contacts_t* contacts_desc, int32_t* contacts) {
+  if (!e || !contacts_desc || !contacts) return fail(MOOG_E_INVALID, "null argument");
+  if (e->n_contacts >= MOOG_MAX_CONTACTS) return fail(MOOG_E_INVALID, "at most MOOG_MAX_CONTACTS contacts observers per engine");
+  SContacts& t = e->contacts[e->n_contacts];
+  int32_t rows[3 * 2 * MOOG_MAX_SLOTS];
+  CtObs d;
+  memset(&d, 0, sizeof d);
+  const char* why = moog_ct_describe(&e->prog, &e->L, contacts_desc, &d, rows);
+  if (why) return fail(MOOG_E_INVALID, why);
+  const size_t rows_bytes = sizeof(int32_t) * 3 * ((size_t)contacts_desc->n_rows_0 + (size_t)contacts_desc->n_rows_1);
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipMalloc(&t.d_rows, rows_bytes));
+  HIPCHK(hipMemcpy(t.d_rows, rows, rows_bytes, hipMemcpyHostToDevice));
+  d.rows = t.d_rows;
+  t.desc = d;
+  *contacts = e->n_contacts++;
+  return MOOG_OK;
+}
+
+int moog_engine_set_contacts_buffer(moog_engine_t* e, int32_t contacts, void* contacts_dev) {
+  if (!e) return fail(MOOG_E_INVALID, "null engine");
+  if (contacts < 0 || contacts >= e->n_contacts) return fail(MOOG_E_INVALID, "no such contacts observer");
+  CtObs& d = e->contacts[contacts].desc;
+  e->n_bound_contacts += (contacts_dev ? 1 : 0) - (d.out ? 1 : 0);
+  d.out = (uint8_t*)contacts_dev;
+  return MOOG_OK;
+}
+
+int moog_engine_observe_contacts(moog_engine_t* e, void* hip_stream) {
+  const int rc = ready(e);
+  if (rc) return rc;
+  return launch_tables(e, (hipStream_t)hip_stream, OBSERVE_CONTACTS);
 }
 
 int moog_engine_kernel_variant(moog_engine_t* e, int32_t* variant, int32_t* late_reset) {

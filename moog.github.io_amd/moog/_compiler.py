@@ -27,7 +27,7 @@ from .state_initialization import distributions as distribs
 Compiled = collections.namedtuple(
     'Compiled', ['program', 'layer_names', 'layer_slots', 'observer_key', 'layout', 'shape_names', 'rule_ref_index',
                  'pstate_slots', 'dynamic_meta', 'color_fn', 'layer_n_init', 'views', 'tables', 'table_rows',
-                 'segmentations', 'segmentation_rows', 'sensors', 'sensor_rows'])
+                 'segmentations', 'segmentation_rows', 'sensors', 'sensor_rows', 'contacts', 'contact_rows'])
 # views: [(observer key, moog_render_t)] of the config's PILRenderers after the first, in dict order -- the engine's extra views
 # (moog_engine_add_view); never part of the program.  tables: [(observer key, moog_table_t)] of the config's SpriteTables, in dict
 # order -- the engine's sprite tables (moog_engine_add_table), never part of the program either; table_rows: {key: [(layer
@@ -36,6 +36,8 @@ Compiled = collections.namedtuple(
 # [(layer name, index in layer)] per row}: mask value v of an 'instance' segmentation is row v - 1.  sensors: [(observer key,
 # moog_sensor_t)] of the config's RaySensors, in dict order -- the engine's ray sensors (moog_engine_add_sensor), never part of
 # the program; sensor_rows: {key: [(layer name, index in layer)] per row}: id v of an 'instance' sensor is row v - 1.
+# contacts: [(observer key, moog_contacts_t)] of the config's Contacts observers, in dict order -- the engine's contacts observers
+# (moog_engine_add_contacts), never part of the program; contact_rows: {key: (rows_0, rows_1)}, each [(layer name, index in layer)].
 # observer_key: the first PILRenderer's key, or None when the config has
 # none (the program's render is then 0 x 0: no frames).
 
@@ -1372,9 +1374,9 @@ def compile_config(state_initializer, physics, task, action_space, observers, ga
     renderers = [(k, o) for k, o in obs_items if isinstance(o, observers_lib.PILRenderer)]
     others = [o for _, o in obs_items
               if not isinstance(o, (observers_lib.PILRenderer, observers_lib.RawState, observers_lib.SpriteTable,
-                                    observers_lib.Segmentation, observers_lib.RaySensor))]
+                                    observers_lib.Segmentation, observers_lib.RaySensor, observers_lib.Contacts))]
     if others:
-        raise NotImplementedError('observers other than PILRenderer, RawState, SpriteTable, Segmentation and RaySensor are not lowered (%s)'
+        raise NotImplementedError('observers other than PILRenderer, RawState, SpriteTable, Segmentation, RaySensor and Contacts are not lowered (%s)'
                                   % (', '.join(sorted(set(type(o).__name__ for o in others))),))
     table_items = [(k, o) for k, o in obs_items if isinstance(o, observers_lib.SpriteTable)]
     if len(table_items) > _abi.MOOG_MAX_TABLES:
@@ -1384,6 +1386,10 @@ def compile_config(state_initializer, physics, task, action_space, observers, ga
     if len(sensor_items) > _abi.MOOG_MAX_SENSORS:
         raise NotImplementedError('at most %d RaySensor observers per config (MOOG_MAX_SENSORS), got %d'
                                   % (_abi.MOOG_MAX_SENSORS, len(sensor_items)))
+    contact_items = [(k, o) for k, o in obs_items if isinstance(o, observers_lib.Contacts)]
+    if len(contact_items) > _abi.MOOG_MAX_CONTACTS:
+        raise NotImplementedError('at most %d Contacts observers per config (MOOG_MAX_CONTACTS), got %d'
+                                  % (_abi.MOOG_MAX_CONTACTS, len(contact_items)))
     seg_items = [(k, o) for k, o in obs_items if isinstance(o, observers_lib.Segmentation)]
     if len(seg_items) > _abi.MOOG_MAX_SEGMENTATIONS:
         raise NotImplementedError('at most %d Segmentation observers per config (MOOG_MAX_SEGMENTATIONS), got %d'
@@ -1486,7 +1492,7 @@ def compile_config(state_initializer, physics, task, action_space, observers, ga
                  [(slot_of[id(sp)], key, cell, table) for sp, key, cell, table in getattr(tr, 'dynamic_meta', [])
                   if id(sp) in slot_of],
                  # PILRenderer(color_to_rgb=<a callable>): evaluated on the host (environment.py _refresh_colors)
-                 color_fn, layer_n_init, views, [], {}, [], {}, [], {})
+                 color_fn, layer_n_init, views, [], {}, [], {}, [], {}, [], {})
     # SpriteTables read the finished layout (rows = the slots of their layers) and leave the program alone
     for key, o in table_items:
         T, rows = o.lower(P, layer_names)
@@ -1497,6 +1503,11 @@ def compile_config(state_initializer, physics, task, action_space, observers, ga
         T, rows = o.lower(P, layer_names)
         c.sensors.append((key, T))
         c.sensor_rows[key] = rows
+    # Contacts too (two row lists)
+    for key, o in contact_items:
+        T, rows = o.lower(P, layer_names)
+        c.contacts.append((key, T))
+        c.contact_rows[key] = rows
     # Segmentations read the finished layout too (ids per sprite slot); whether the mask rasteriser can hold such a frame
     # (moog_engine_raster_path's criteria) is checked here, so that the refusal comes when the config is lowered
     for key, o in seg_items:

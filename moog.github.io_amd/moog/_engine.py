@@ -24,6 +24,7 @@ SYMBOLS = (
     'moog_engine_add_view', 'moog_engine_set_view_image', 'moog_engine_view_raster_path',
     'moog_engine_add_table', 'moog_engine_set_table_buffer', 'moog_engine_observe_tables',
     'moog_engine_add_sensor', 'moog_engine_set_sensor_buffer', 'moog_engine_observe_sensors',
+    'moog_engine_add_contacts', 'moog_engine_set_contacts_buffer', 'moog_engine_observe_contacts',
     'moog_engine_add_segmentation', 'moog_engine_set_segmentation_image',
 )
 
@@ -86,6 +87,9 @@ def load_library(path=None):
     lib.moog_engine_add_sensor.argtypes = [vp, ctypes.POINTER(_abi.Sensor), ctypes.POINTER(i32)]
     lib.moog_engine_set_sensor_buffer.argtypes = [vp, i32, vp]
     lib.moog_engine_observe_sensors.argtypes = [vp, vp]
+    lib.moog_engine_add_contacts.argtypes = [vp, ctypes.POINTER(_abi.Contacts), ctypes.POINTER(i32)]
+    lib.moog_engine_set_contacts_buffer.argtypes = [vp, i32, vp]
+    lib.moog_engine_observe_contacts.argtypes = [vp, vp]
     lib.moog_engine_add_segmentation.argtypes = [vp, ctypes.POINTER(_abi.Segmentation), ctypes.POINTER(i32)]
     lib.moog_engine_set_segmentation_image.argtypes = [vp, i32, vp]
     lib.moog_engine_read_draw_records.argtypes = [vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i32)]

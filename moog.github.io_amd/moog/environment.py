@@ -8,7 +8,8 @@ observation {'image': uint8[N,H,W,3]} -- all torch tensors on the device; a conf
 PILRenderers gets one such tensor per renderer key (the engine's extra views), one with none only
 its RawState entries; a SpriteTable observer's entry is its float32 / float16 tensor [N, rows, columns], rewritten in place
 like the frames, a Segmentation observer's its uint8 id image [N, H, W], drawn with the frames, a RaySensor observer's its
-float32 / float16 readings [N, rays, 2], kept beside the tables' tensors and rewritten with them.
+float32 / float16 readings [N, rays, 2], kept beside the tables' tensors and rewritten with them, a Contacts observer's its
+uint8 overlap flags [N, R0, R1] or [N, R0, layers], kept and rewritten likewise.
 Auto-reset follows environment.py:100-101 per env: the call after a LAST
 timestep ignores that env's action and returns a FIRST timestep.
 
@@ -153,6 +154,7 @@ class BatchedEnvironment(object):
         self._attach_views()
         self._attach_tables()
         self._attach_sensors()
+        self._attach_contacts()
         self._attach_segmentations()
         self._out = _abi.StepOut()
         self._out.reward = ctypes.cast(self.reward.data_ptr(), ctypes.POINTER(ctypes.c_double))
@@ -265,6 +267,24 @@ class BatchedEnvironment(object):
                 self._handle, idx.value, ctypes.c_void_p(self.tables[key].data_ptr())))
             self._sensor_index[key] = idx.value
 
+    def _attach_contacts(self):
+        """The config's Contacts observers: a contacts observer of the engine each (moog_engine_add_contacts), evaluated into
+        its own uint8 tensor (kept beside the tables' tensors, `tables`) by every reset / step call and by observation()."""
+        self._contacts_index = {}
+        for key, desc in self.compiled.contacts:
+            idx = ctypes.c_int32()
+            with self._torch.cuda.device(self.device):
+                _engine.check(self._lib, self._lib.moog_engine_add_contacts(self._handle, ctypes.byref(desc), ctypes.byref(idx)))
+            _engine.check(self._lib, self._lib.moog_engine_set_contacts_buffer(
+                self._handle, idx.value, ctypes.c_void_p(self.tables[key].data_ptr())))
+            self._contacts_index[key] = idx.value
+
+    def contact_rows(self, key):
+        """(rows_0, rows_1) of the Contacts observer `key`: [(layer name, index in layer)] for every row of each argument --
+        the rows of a SpriteTable over the same layers.  In 'layer' mode column l is the l-th layer of `layers_1`."""
+        rows_0, rows_1 = self.compiled.contact_rows[key]
+        return list(rows_0), list(rows_1)
+
     def ray_rows(self, key):
         """[(layer name, index in layer)] for every row of the RaySensor observer `key`: id v of an 'instance' sensor is row
         v - 1 (the rows of a SpriteTable over the same layers); id v of a 'layer' sensor is the v-th chosen layer; 0 is no
@@ -283,17 +303,23 @@ class BatchedEnvironment(object):
         if self.compiled.sensors:
             with self._torch.cuda.device(self.device):
                 _engine.check(self._lib, self._lib.moog_engine_observe_sensors(self._handle, self._stream()))
+        if self.compiled.contacts:
+            with self._torch.cuda.device(self.device):
+                _engine.check(self._lib, self._lib.moog_engine_observe_contacts(self._handle, self._stream()))
 
     @staticmethod
     def allocate_table_buffers(torch, compiled, n, device):
         """{key: float32 / float16 [n, rows, columns]} for the config's SpriteTables and {key: float32 / float16
-        [n, rays, 2]} for its RaySensors."""
+        [n, rays, 2]} for its RaySensors and {key: uint8 [n, R0, R1] or [n, R0, layers]} for its Contacts observers."""
+        from .observers import contacts as contacts_lib
         bufs = {key: torch.zeros((n, int(T.n_rows), int(T.n_cols)), device=device,
                                  dtype=torch.float16 if T.dtype == _abi.MOOG_TABLE_F16 else torch.float32)
                 for key, T in compiled.tables}
         bufs.update({key: torch.zeros((n, int(T.n_rays), 2), device=device,
                                       dtype=torch.float16 if T.dtype == _abi.MOOG_TABLE_F16 else torch.float32)
                      for key, T in compiled.sensors})
+        bufs.update({key: torch.zeros((n,) + contacts_lib.contacts_shape(T), device=device, dtype=torch.uint8)
+                     for key, T in compiled.contacts})
         return bufs
 
     def table_rows(self, key):
@@ -686,6 +712,7 @@ class BatchedEnvironment(object):
             self.tables = self.allocate_table_buffers(torch, new_c, self.num_envs, self.device)
             self._attach_tables()
             self._attach_sensors()   # (other capacities, other rows and ids; the readings under them at once)
+            self._attach_contacts()  # (the rows move: new descriptors over the new tensors)
             self._observe_tables()
             self._attach_segmentations()   # (other capacities, other ids; the tensors keep their size)
             if f32:
@@ -898,9 +925,11 @@ class BatchedEnvironment(object):
         return self._observation()
 
     def observation_spec(self):
-        from .observers import raw_state, sprite_table
+        from .observers import contacts as contacts_lib, raw_state, sprite_table
         tables = dict(self.compiled.tables)   # (a SpriteTable's shape follows from this environment's layer capacities)
-        return {k: sprite_table.table_spec(tables[k]) if k in tables else o.observation_spec()
+        contacts = dict(self.compiled.contacts)   # (a Contacts observer's too)
+        return {k: sprite_table.table_spec(tables[k]) if k in tables
+                else contacts_lib.contacts_spec(contacts[k]) if k in contacts else o.observation_spec()
                 for k, o in self.observers.items() if not isinstance(o, raw_state.RawState)}
 
     def action_spec(self):
@@ -1237,6 +1266,9 @@ class SubBatchedEnvironment(object):
 
     def ray_rows(self, key):
         return self.parts[0].ray_rows(key)
+
+    def contact_rows(self, key):
+        return self.parts[0].contact_rows(key)
 
     def ray_directions(self, key):
         return self.parts[0].ray_directions(key)

@@ -5,12 +5,13 @@ from .pil_renderer import PILRenderer
 from .raw_state import RawState
 from .sprite_table import SpriteTable
 from .ray_sensor import RaySensor
+from .contacts import Contacts
 from .segmentation import Segmentation
 
 
 class AbstractObserver(object):
     """abstract_observer.py:7-36: `__call__(state)` and `observation_spec()`.  The engine's observers are parameter
-    records the rasteriser / the raw-state reader / the table kernel are configured from (PILRenderer, RawState, SpriteTable, Segmentation, RaySensor); a config-local subclass
+    records the rasteriser / the raw-state reader / the table kernel are configured from (PILRenderer, RawState, SpriteTable, Segmentation, RaySensor, Contacts); a config-local subclass
     has no device form and is refused when the environment is built."""
 
     def __call__(self, state):
