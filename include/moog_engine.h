@@ -833,6 +833,23 @@ int moog_engine_set_action_dtype(moog_engine_t* e, int32_t float32);
  * word for word, those after m calls with k = 1.  A fault does not end the repeat.  A call with injected uniforms
  * (moog_inject_t: a per-call stream) is refused while k > 1. */
 int moog_engine_set_action_repeat(moog_engine_t* e, int32_t k, int32_t* count_dev);
+/* Action sequence (open-loop rollout): moog_engine_step at action repeat n_steps (1 <= n_steps <= MOOG_MAX_ACTION_REPEAT), except
+ * that env-step j of the call reads an action block of its own and leaves its reward behind -- one launch of the step kernel,
+ * the record on chip between the steps, what a planner's roll-out (the reference's SimulationEnvironment, sim_step) needs.
+ * actions_dev: n_steps blocks, each laid out as moog_engine_step takes one (and of the dtype moog_engine_set_action_dtype
+ * says), block j at actions_dev + j * action_step_bytes.  rewards_dev: float64, the reward of step j of env i at
+ * rewards_dev[j * reward_step_elems + i]; the steps an env does not take -- those behind the step m that ended its episode,
+ * every step of an env the call reset instead -- hold 0.0.  The two strides let a sub-batch read and write its slice of
+ * whole-batch [n_steps][N]... arrays in place.  Everything else is the repeat's: the launch order, the reset pool and the late
+ * reset; out->reward = ((r_1 + r_2) + ...) + r_m, step_type / discount of step m; frames, tables, sensors, contacts, views
+ * and segmentations once, after the call; the count buffer registered with moog_engine_set_action_repeat(e, 1, count_dev)
+ * receives m (0 for a reset env).  n_steps = 1 computes exactly what moog_engine_step computes, plus rewards_dev[0 .. n_envs).
+ * The engine's action-repeat setting is not changed.  MOOG_E_INVALID: null engine / actions / rewards, n_steps out of range;
+ * MOOG_E_UNSUPPORTED: injected uniforms (one env-step's stream, as with the repeat), an engine whose action repeat is above 1
+ * (a hold count per entry is not available).  Timed as MOOG_K_STEP. */
+int moog_engine_step_sequence(moog_engine_t* e, const void* actions_dev, int32_t n_steps, int64_t action_step_bytes,
+                              double* rewards_dev, int64_t reward_step_elems, const moog_inject_t* inject,
+                              const moog_step_out_t* out, void* hip_stream);
 /* env.physics.step(env.state) only (tests/runtime_benchmark.py:101-107). */
 int moog_engine_physics_only(moog_engine_t* e, const moog_inject_t* inject,
                              void* hip_stream);

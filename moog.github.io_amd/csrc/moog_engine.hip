@@ -982,6 +982,7 @@ static KArgs make_args(moog_engine* e, const void* actions, const moog_inject_t*
   a.act_f32 = e->act_f32;
   a.repeat = mode == MODE_STEP ? e->action_repeat : 1;
   a.repeat_count = mode == MODE_STEP ? e->repeat_count : nullptr;
+  a.act_step_bytes = 0; a.reward_seq = nullptr; a.reward_seq_stride = 0;   // (moog_engine_step_sequence sets the three)
   a.xstack_off = e->xstack_off;
   a.watch = (mode == MODE_STEP) ? e->watch : nullptr; a.watch_off = e->watch_off;
   a.fops = e->d_fops; a.n_fops = e->n_fops;
@@ -1002,7 +1003,8 @@ static KArgs make_args(moog_engine* e, const void* actions, const moog_inject_t*
 static bool steps_specialised(const moog_engine* e) { return e->spec_launch && e->step_dbg == 0 && !e->watch; }
 
 static void launch_step(moog_engine* e, hipStream_t s, const KArgs& a) {
-  // (the second six: the kernels with the action-repeat loop, for calls that take more than one env-step)
+  // (the second six: the kernels with the action-repeat loop, for calls that take more than one env-step and for action
+  //  sequences, whose per-step rewards the one-step kernels do not write)
   static const moog_step_launch_fn launch[12] = {moog_launch_step_f3, moog_launch_step_f4, moog_launch_step_t3,
                                                  moog_launch_step_t4, moog_launch_step_m3, moog_launch_step_m4,
                                                  moog_launch_step_f3r, moog_launch_step_f4r, moog_launch_step_t3r,
@@ -1012,7 +1014,7 @@ static void launch_step(moog_engine* e, hipStream_t s, const KArgs& a) {
     return;
   }
   const bool full = e->maze_kernel && !e->late_reset;
-  launch[(a.repeat > 1 ? 6 : 0) + (full ? 4 : (e->dynamic_rules ? 2 : 0)) + (e->step_wps == 4 ? 1 : 0)](e->n_envs, e->step_lds, s, a);
+  launch[((a.repeat > 1 || a.reward_seq) ? 6 : 0) + (full ? 4 : (e->dynamic_rules ? 2 : 0)) + (e->step_wps == 4 ? 1 : 0)](e->n_envs, e->step_lds, s, a);
 }
 
 // What the draw-record emitter needs (moog_draw_record.h): by value in the step kernel's and the derive kernel's arguments.
@@ -1305,17 +1307,20 @@ int moog_engine_reset(moog_engine_t* e, const uint8_t* env_mask_dev, const moog_
   return MOOG_OK;
 }
 
-int moog_engine_step(moog_engine_t* e, const void* actions_dev, const moog_inject_t* inject,
-                     const moog_step_out_t* out, void* hip_stream) {
-  int rc = ready(e);
-  if (rc) return rc;
-  if (!actions_dev) return fail(MOOG_E_INVALID, "null actions");
-  if (out && out->image && e->frameless) return fail(MOOG_E_INVALID, FRAMELESS_MSG);
-  if (e->action_repeat > 1 && inject && inject->uniforms)
-    return fail(MOOG_E_UNSUPPORTED, "injected uniforms are one call's stream: they cannot feed the several env-steps of an action repeat (moog_engine_set_action_repeat(e, 1, ...) first)");
+// One MODE_STEP call: moog_engine_step (n_steps = 0: the engine's action repeat, one action block) or
+// moog_engine_step_sequence (n_steps >= 1 action blocks act_step_bytes apart, per-step rewards to rewards_dev).
+static int step_call(moog_engine* e, const void* actions_dev, int32_t n_steps, int64_t act_step_bytes, double* rewards_dev,
+                     int64_t reward_step_elems, const moog_inject_t* inject, const moog_step_out_t* out, void* hip_stream) {
   hipStream_t s = (hipStream_t)hip_stream;
   // (envs whose episode ended in the previous call are reset inside the step kernel, environment.py:100-101)
   KArgs a = make_args(e, actions_dev, inject, out, MODE_STEP, nullptr);
+  if (n_steps > 0) {
+    a.repeat = n_steps;
+    a.act_step_bytes = act_step_bytes;
+    a.reward_seq = rewards_dev;
+    a.reward_seq_stride = reward_step_elems;
+  }
+  int rc;
   const bool emit = out && out->image && step_emits_draw(e);
   if (emit) a.draw = emit_args(e, e->views[0]);
   if (e->sched_pending) {   // the order computed from the previous step's costs
@@ -1340,6 +1345,34 @@ int moog_engine_step(moog_engine_t* e, const void* actions_dev, const moog_injec
   if ((rc = launch_tables(e, s)) != MOOG_OK) return rc;
   if (out && out->image) return launch_frames(e, out->image, s, emit);
   return MOOG_OK;
+}
+
+int moog_engine_step(moog_engine_t* e, const void* actions_dev, const moog_inject_t* inject,
+                     const moog_step_out_t* out, void* hip_stream) {
+  int rc = ready(e);
+  if (rc) return rc;
+  if (!actions_dev) return fail(MOOG_E_INVALID, "null actions");
+  if (out && out->image && e->frameless) return fail(MOOG_E_INVALID, FRAMELESS_MSG);
+  if (e->action_repeat > 1 && inject && inject->uniforms)
+    return fail(MOOG_E_UNSUPPORTED, "injected uniforms are one call's stream: they cannot feed the several env-steps of an action repeat (moog_engine_set_action_repeat(e, 1, ...) first)");
+  return step_call(e, actions_dev, 0, 0, nullptr, 0, inject, out, hip_stream);
+}
+
+int moog_engine_step_sequence(moog_engine_t* e, const void* actions_dev, int32_t n_steps, int64_t action_step_bytes,
+                              double* rewards_dev, int64_t reward_step_elems, const moog_inject_t* inject,
+                              const moog_step_out_t* out, void* hip_stream) {
+  int rc = ready(e);
+  if (rc) return rc;
+  if (!actions_dev) return fail(MOOG_E_INVALID, "null actions");
+  if (!rewards_dev) return fail(MOOG_E_INVALID, "null rewards");
+  if (n_steps < 1 || n_steps > MOOG_MAX_ACTION_REPEAT)
+    return fail(MOOG_E_INVALID, "sequence length out of range (1 .. MOOG_MAX_ACTION_REPEAT)");
+  if (out && out->image && e->frameless) return fail(MOOG_E_INVALID, FRAMELESS_MSG);
+  if (inject && inject->uniforms)
+    return fail(MOOG_E_UNSUPPORTED, "injected uniforms are one env-step's stream: they cannot feed the env-steps of an action sequence (moog_engine_step takes them)");
+  if (e->action_repeat > 1)
+    return fail(MOOG_E_UNSUPPORTED, "an action sequence on an engine with an action repeat above 1 (a hold count per entry) is not available: moog_engine_set_action_repeat(e, 1, ...) first");
+  return step_call(e, actions_dev, n_steps, action_step_bytes, rewards_dev, reward_step_elems, inject, out, hip_stream);
 }
 
 int moog_engine_physics_only(moog_engine_t* e, const moog_inject_t* inject, void* hip_stream) {

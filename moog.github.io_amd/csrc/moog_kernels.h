@@ -161,6 +161,12 @@ struct KArgs {
   RmEmit draw;           // draw.out != null: a step (MODE_STEP) also writes the env's draw record (moog_draw_record.h) for the raster launch behind it
   int32_t repeat;        // action repeat (moog_engine_set_action_repeat): env-steps a MODE_STEP call takes per env, >= 1
   int32_t* repeat_count; // [n_envs] the env-steps the call took (0: the call reset the env instead), or null
+  // action sequence (moog_engine_step_sequence; read by the kernels with the repeat loop only): step j of the call reads its
+  // action block at actions + j * act_step_bytes (0: every step reads the same block, the action repeat) and stores its reward
+  // to reward_seq[j * reward_seq_stride + env]; the steps an env does not take hold 0.0
+  int64_t act_step_bytes;
+  double* reward_seq;    // [repeat][...] or null
+  int64_t reward_seq_stride;   // elements between the rows of two steps
 };
 
 enum { MODE_STEP = 0, MODE_PHYSICS = 1, MODE_RESET_MASK = 2, MODE_FILL = 3 };
@@ -174,6 +180,13 @@ enum { MODE_STEP = 0, MODE_PHYSICS = 1, MODE_RESET_MASK = 2, MODE_FILL = 3 };
 #endif
 
 extern __shared__ __attribute__((aligned(16))) unsigned char moog_lds[];
+
+// Action sequence: the rewards of the steps from `from` on, which the env does not take, are 0.0 (lane j holds step j: a call
+// takes at most MOOG_MAX_ACTION_REPEAT = 64 steps)
+static_assert(MOOG_MAX_ACTION_REPEAT <= 64, "one lane per step of a sequence");
+__device__ __forceinline__ void reward_seq_zero(const KArgs& a, int env, int lane, int from) {
+  if (a.reward_seq && lane >= from && lane < a.repeat) a.reward_seq[(long long)lane * a.reward_seq_stride + env] = 0.0;
+}
 
 // lds: this wave's record area (the whole dynamic LDS of a one-wave workgroup)
 __device__ inline void bind_env(Env& e, const KArgs& a, int env, unsigned char* lds = moog_lds, int lane = (int)threadIdx.x) {
@@ -642,6 +655,7 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
         // that carries everything steps 1.4 - 2.7 times slower, profiles/r04_variant_tax.txt).  The env is marked and left
         // as it is; the full reset kernel, launched behind this one, opens its episode and releases the pool's lock.
         if (e.lane == 0) { a.late_mask[env] = 1; if (a.repeat_count) a.repeat_count[env] = 0; }
+        if constexpr (REPEAT) reward_seq_zero(a, env, e.lane, 0);
         return;
       }
       env_reset<DYN>(e);
@@ -660,6 +674,7 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
       }
 #endif
     }
+    if constexpr (REPEAT) reward_seq_zero(a, env, e.lane, 0);
     emit_draw_record(e, a, env);   // (before the record's stores: a wave waits once for its stores to drain, at its end)
     store_record(e, a.H, a.L, gf, gq, a.fault_flag);
     if (DYN && held) pool_release(a, env, e.lane);
@@ -672,6 +687,8 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
   // between them; the repeat ends with the first step whose task asks for a reset.  Everything a call derives from the record
   // is derived again for every step (the boxes below), so step j computes what a launch of its own would.  Wave uniform:
   // the count, the flag and the reward so far (lane 0's values, the ones the outputs have always held) live in scalar registers.
+  // Action sequence (moog_engine_step_sequence): step j reads the j-th action block, at the call's address plus a wave-uniform
+  // offset, and leaves its reward in reward_seq.
   const int reps = REPEAT ? a.repeat : 1;
   int done = 0, sr = 0;
   double rsum = 0;
@@ -691,24 +708,26 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
     for (int r = 0; r < n_rules; ++r)
       if (P->rules[r].parent < 0) rule_step<DYN>(e, r);
     const bool af32 = a.act_f32 != 0;
+    const void* actions = a.actions;
+    if constexpr (REPEAT) actions = static_cast<const char*>(a.actions) + (long long)done * a.act_step_bytes;
     if (uni(P->n_actions) > 1) {   // composite.py:61-62: every sub-space, in keyword order
       const int na = uni(P->n_actions);
       for (int k = 0; k < na; ++k) {
         double x, y;
-        if (af32) { const float* act = reinterpret_cast<const float*>(a.actions) + (size_t)2 * na * env; x = act[2 * k]; y = act[2 * k + 1]; }
-        else { const double* act = reinterpret_cast<const double*>(a.actions) + (size_t)2 * na * env; x = act[2 * k]; y = act[2 * k + 1]; }
+        if (af32) { const float* act = reinterpret_cast<const float*>(actions) + (size_t)2 * na * env; x = act[2 * k]; y = act[2 * k + 1]; }
+        else { const double* act = reinterpret_cast<const double*>(actions) + (size_t)2 * na * env; x = act[2 * k]; y = act[2 * k + 1]; }
         action_step(e, k, x, y, (int)x, af32);
       }
     } else {
       double ax = 0, ay = 0;
       int ga = 4;
-      if (P->action.kind == MOOG_ACTION_GRID) ga = reinterpret_cast<const int32_t*>(a.actions)[env];
+      if (P->action.kind == MOOG_ACTION_GRID) ga = reinterpret_cast<const int32_t*>(actions)[env];
       else if (af32) {
-        ax = reinterpret_cast<const float*>(a.actions)[2 * env];
-        ay = reinterpret_cast<const float*>(a.actions)[2 * env + 1];
+        ax = reinterpret_cast<const float*>(actions)[2 * env];
+        ay = reinterpret_cast<const float*>(actions)[2 * env + 1];
       } else {
-        ax = reinterpret_cast<const double*>(a.actions)[2 * env];
-        ay = reinterpret_cast<const double*>(a.actions)[2 * env + 1];
+        ax = reinterpret_cast<const double*>(actions)[2 * env];
+        ay = reinterpret_cast<const double*>(actions)[2 * env + 1];
       }
       action_step(e, 0, ax, ay, ga, af32);
     }
@@ -723,6 +742,9 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
     double rj;
     { PROF_T0; rj = task_reward<DYN>(e, sc, &sr); PROF_ADD(e, 11); }
     wsync();
+    if constexpr (REPEAT) {
+      if (a.reward_seq && e.lane == 0) a.reward_seq[(long long)done * a.reward_seq_stride + env] = rj;
+    }
     if (!REPEAT || reps <= 1) { rsum = rj; done = 1; break; }   // (a single step: its reward and flag as they are)
     sr = uni(sr);
     rj = uni_f64(rj);
@@ -736,6 +758,7 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
     if (a.step_type) a.step_type[env] = sr ? 2 : 1;
     if (a.repeat_count) a.repeat_count[env] = done;
   }
+  if constexpr (REPEAT) reward_seq_zero(a, env, e.lane, done);
   SEC(e, SEC_STORE);
   emit_draw_record(e, a, env);   // (before the record's stores: a wave waits once for its stores to drain, at its end)
   store_record(e, a.H, a.L, gf, gq, a.fault_flag);

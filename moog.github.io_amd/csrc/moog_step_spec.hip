@@ -27,7 +27,8 @@ unsigned long long moog_spec_kargs_size(void) { return sizeof(KArgs); }
 // (the program the kernel was compiled for: the engine compares it with its own before using the kernel)
 const void* moog_spec_program(void) { return &MOOG_SPEC_PROGRAM; }
 
-// (two kernels: the one-step kernel, and the one with the action-repeat loop for calls with KArgs::repeat > 1)
+// (two kernels: the one-step kernel, and the one with the action-repeat loop for calls with KArgs::repeat > 1 and for action
+//  sequences, KArgs::reward_seq)
 int moog_spec_configure(size_t lds) {
   const int rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(moog_step_kernel<MOOG_STEP_DYN != 0, MOOG_STEP_WPS, MOOG_STEP_DYN, false>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -37,7 +38,7 @@ int moog_spec_configure(size_t lds) {
 }
 
 void moog_spec_launch(int n_envs, size_t lds, hipStream_t s, const KArgs* a) {
-  if (a->repeat > 1)
+  if (a->repeat > 1 || a->reward_seq)   // (a sequence of one step too: the one-step kernel knows nothing of KArgs::reward_seq)
     hipLaunchKernelGGL((moog_step_kernel<MOOG_STEP_DYN != 0, MOOG_STEP_WPS, MOOG_STEP_DYN, true>), dim3(n_envs), dim3(MOOG_STEP_THREADS), lds, s, *a);
   else
     hipLaunchKernelGGL((moog_step_kernel<MOOG_STEP_DYN != 0, MOOG_STEP_WPS, MOOG_STEP_DYN, false>), dim3(n_envs), dim3(MOOG_STEP_THREADS), lds, s, *a);

@@ -26,6 +26,7 @@ SYMBOLS = (
     'moog_engine_add_sensor', 'moog_engine_set_sensor_buffer', 'moog_engine_observe_sensors',
     'moog_engine_add_contacts', 'moog_engine_set_contacts_buffer', 'moog_engine_observe_contacts',
     'moog_engine_add_segmentation', 'moog_engine_set_segmentation_image',
+    'moog_engine_step_sequence',
 )
 
 _LIB = None
@@ -69,6 +70,8 @@ def load_library(path=None):
                                       ctypes.POINTER(_abi.StepOut), vp]
     lib.moog_engine_step.argtypes = [vp, vp, ctypes.POINTER(_abi.Inject),
                                      ctypes.POINTER(_abi.StepOut), vp]
+    lib.moog_engine_step_sequence.argtypes = [vp, vp, i32, i64, vp, i64, ctypes.POINTER(_abi.Inject),
+                                              ctypes.POINTER(_abi.StepOut), vp]
     lib.moog_engine_physics_only.argtypes = [vp, ctypes.POINTER(_abi.Inject), vp]
     lib.moog_engine_render.argtypes = [vp, vp, vp]
     lib.moog_engine_set_schedule.argtypes = [vp, vp, vp]

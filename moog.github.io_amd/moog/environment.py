@@ -799,6 +799,20 @@ class BatchedEnvironment(object):
                 self._action_f32 = f32
             a = (a if f32 else a.to(torch.float64)).contiguous()
             assert a.shape == (self.num_envs, 2)
+        self._step_host_rules()
+        inj, keep = self._inject(injected_uniforms)
+        with torch.cuda.device(self.device):
+            _engine.check(self._lib, self._lib.moog_engine_step(
+                self._handle, ctypes.c_void_p(a.data_ptr()), ctypes.byref(inj) if inj else None,
+                ctypes.byref(self._out if self._color_fn is None else self._out_noimg), self._stream()))
+        if self._color_fn is not None:
+            self._render_with_colors()
+        self._last_action = a
+        self._after_step_call(injected_uniforms is not None)
+        del keep
+        return self._timestep()
+
+    def _step_host_rules(self):
         if self._host_rules or self._meta_state_initializer is not None:
             # environment.py:100-104: an auto-reset re-initialises the meta-state; either way
             # every rule steps once per call
@@ -817,24 +831,136 @@ class BatchedEnvironment(object):
                         self._meta_state[i] = self._new_meta_state()
                     for r in self._host_rules:
                         r.step(None, self._meta_state[i])
-        inj, keep = self._inject(injected_uniforms)
-        with torch.cuda.device(self.device):
-            _engine.check(self._lib, self._lib.moog_engine_step(
-                self._handle, ctypes.c_void_p(a.data_ptr()), ctypes.byref(inj) if inj else None,
-                ctypes.byref(self._out if self._color_fn is None else self._out_noimg), self._stream()))
-        if self._color_fn is not None:
-            self._render_with_colors()
-        self._last_action = a
+
+    def _after_step_call(self, injected):
         # Programs whose rules append to layers can overflow a layer's capacity at any step:
         # surface that (one host sync per step; set check_faults = False to opt out).
-        if self.check_faults == 'sync' or (self.check_faults and (injected_uniforms is not None or self._dynamic_layers)):
+        if self.check_faults == 'sync' or (self.check_faults and (injected or self._dynamic_layers)):
             self.raise_faults()
-        del keep
         if self._auto_capacity and self._dynamic_layers:
             self._n_step_calls += 1
             if self._fit_after > 0 and self._n_step_calls == self._fit_after:
                 self.fit_layer_capacity()   # (once; sets the margin _grow_if_close works with from here on)
             self._grow_if_close()
+
+    # -- open-loop rollouts (include/moog_engine.h moog_engine_step_sequence) -----------------
+    def _sequence_shape(self, n):
+        """The shape of a rollout's actions for n envs, as the error messages name it."""
+        if self._composite:
+            return '[T, %d, %d, 2] (or a dict {key: [T, %d, 2] / [T, %d]} with the keys %s)' % (
+                n, len(self.action_space.action_keys), n, n, list(self.action_space.action_keys))
+        return '[T, %d]' % n if self._is_grid else '[T, %d, 2]' % n
+
+    def _pack_sequence(self, actions, n=None):
+        """A rollout's actions as ONE device tensor [T, n, ...], step t's block laid out as step() hands one to the engine
+        (float32 Joystick actions stay float32).  ValueError: a shape or a dict key that does not fit, T out of range."""
+        torch = self._torch
+        n = self.num_envs if n is None else n
+
+        def bad(got):
+            return ValueError('rollout: actions of shape %s, expected %s with 1 <= T <= %d'
+                              % (got, self._sequence_shape(n), _abi.MOOG_MAX_ACTION_REPEAT))
+
+        def shape_of(v):
+            return tuple(v.shape) if hasattr(v, 'shape') else tuple(np.shape(v))
+
+        if self._composite:
+            keys = list(self.action_space.action_keys)
+            if isinstance(actions, dict):
+                if set(actions) != set(keys):
+                    raise ValueError('rollout: composite action keys %s, expected %s, each [T, %d, 2] or [T, %d]'
+                                     % (sorted(actions), keys, n, n))
+                vs = [torch.as_tensor(actions[key], device=self.device).to(torch.float64) for key in keys]
+                T = vs[0].shape[0] if vs[0].dim() >= 2 else -1
+                a = torch.zeros((max(T, 0), n, len(keys), 2), dtype=torch.float64, device=self.device)
+                for i, v in enumerate(vs):
+                    if tuple(v.shape) == (T, n):   # Grid move indices
+                        a[:, :, i, 0] = v
+                    elif tuple(v.shape) == (T, n, 2):
+                        a[:, :, i, :] = v
+                    else:
+                        raise bad({key: shape_of(actions[key]) for key in keys})
+            else:
+                a = torch.as_tensor(actions, device=self.device).to(torch.float64)
+                if a.dim() != 4 or tuple(a.shape[1:]) != (n, len(keys), 2):
+                    raise bad(tuple(a.shape))
+            if self._n_actions == 1:   # a Composite of one space is that space's own buffer (_pack_composite)
+                a = a[:, :, 0, :]
+                a = a[:, :, 0].to(torch.int32) if self.compiled.program.action.kind == _abi.MOOG_ACTION_GRID else a
+            else:
+                a = a.reshape(a.shape[0], n, 2 * self._n_actions)
+        elif self._is_grid:
+            a = torch.as_tensor(actions, device=self.device)
+            if a.dim() != 2 or a.shape[1] != n:
+                raise bad(tuple(a.shape))
+            a = a.to(torch.int32)
+        else:
+            a = torch.as_tensor(actions, device=self.device)
+            if a.dim() != 3 or tuple(a.shape[1:]) != (n, 2):
+                raise bad(tuple(a.shape))
+            a = a if a.dtype == torch.float32 else a.to(torch.float64)
+        if not 1 <= a.shape[0] <= _abi.MOOG_MAX_ACTION_REPEAT:
+            raise bad(tuple(a.shape))
+        return a if a[0].is_contiguous() and (a.shape[0] == 1 or a.stride(0) >= a[0].numel()) else a.contiguous()
+
+    @staticmethod
+    def _sequence_length(actions):
+        if isinstance(actions, dict):
+            actions = next(iter(actions.values())) if actions else ()
+        return len(actions)
+
+    def _check_rollout(self, T):
+        """T as an int, or the reason this engine cannot run a sequence of T env-steps inside one launch."""
+        if not 1 <= T <= _abi.MOOG_MAX_ACTION_REPEAT:
+            raise ValueError('rollout: T = %d actions per env, expected 1 .. %d' % (T, _abi.MOOG_MAX_ACTION_REPEAT))
+        if self._action_repeat > 1:
+            raise NotImplementedError('rollout on an engine with action_repeat=%d (a hold count per sequence entry) is not '
+                                      'available: set_action_repeat(1) first' % self._action_repeat)
+        return self._check_action_repeat(T)   # (T env-steps inside one launch: what a repeat of T cannot do, this cannot either)
+
+    def rollout(self, actions):
+        """Open loop: T env-steps with T different actions inside one launch of the step kernel, no observation in between
+        (a planner's roll-out: random shooting, CEM / MPC, the leaves of a tree search; with snapshot() / restore(), the
+        reference's SimulationEnvironment).  actions: [T, N, 2] (Joystick; float32 stays float32, as in step()), [T, N]
+        (Grid), [T, N, n_spaces, 2] or a dict of [T, N, 2] / [T, N] (Composite); numpy or device tensors, 1 <= T <=
+        MOOG_MAX_ACTION_REPEAT.  Returns (timestep, rewards, count):
+          rewards   float64 [T, N]: the reward of every env-step; 0.0 for the steps an env did not take (those behind the
+                    step that ended its episode, every step of an env the call reset instead)
+          count     `repeat_count`, int32 [N]: the env-steps each env took (0: the call reset the env, a FIRST timestep)
+          timestep  what a step() at action_repeat=T returns: the rewards' sum in step order, the step_type / discount of
+                    the last step taken, the observations after it.
+        The state after the call is, bit for bit, the state after count single step() calls with the same actions."""
+        T = self._check_rollout(self._sequence_length(actions))   # (refusals first: they need no device)
+        torch = self._torch
+        a = self._pack_sequence(actions)
+        with torch.cuda.device(self.device):
+            rewards = torch.empty((T, self.num_envs), dtype=torch.float64, device=self.device)
+        ts = self._rollout_packed(a, rewards)
+        return ts, rewards, self.repeat_count
+
+    def _rollout_packed(self, a, rewards):
+        """rollout() on packed actions [T, n, ...] and a reward tensor [T, n] of the caller's, either one possibly a slice of
+        a whole batch's (rows further apart than their length: the engine takes the two strides)."""
+        torch = self._torch
+        T = self._check_rollout(int(a.shape[0]))
+        assert a.shape[1] == self.num_envs and a[0].is_contiguous(), (tuple(a.shape), a.stride())
+        assert tuple(rewards.shape) == (T, self.num_envs) and rewards.dtype == torch.float64 and rewards.stride(1) == 1
+        self._poll_faults()
+        if a.dtype != torch.int32 and not self._composite:
+            f32 = a.dtype == torch.float32
+            if f32 != self._action_f32:
+                _engine.check(self._lib, self._lib.moog_engine_set_action_dtype(self._handle, 1 if f32 else 0))
+                self._action_f32 = f32
+        self._step_host_rules()   # (T == 1: _check_rollout refuses host-side rules beyond that)
+        with torch.cuda.device(self.device):
+            _engine.check(self._lib, self._lib.moog_engine_step_sequence(
+                self._handle, ctypes.c_void_p(a.data_ptr()), T, a.stride(0) * a.element_size(),
+                ctypes.c_void_p(rewards.data_ptr()), rewards.stride(0), None,
+                ctypes.byref(self._out if self._color_fn is None else self._out_noimg), self._stream()))
+        if self._color_fn is not None:
+            self._render_with_colors()
+        self._last_action = a
+        self._after_step_call(False)
         return self._timestep()
 
     def _pack_composite(self, action):
@@ -1224,6 +1350,25 @@ class SubBatchedEnvironment(object):
             self.step_async(g, action[g * m:(g + 1) * m])
         self._join()
         return self._timestep()
+
+    def rollout(self, actions):
+        """BatchedEnvironment.rollout of the whole batch, synchronous: the actions are packed once, every sub-batch runs its
+        [T, num_envs / G, ...] slice of them on its own stream and writes its slice of one [T, num_envs] reward tensor (no
+        copies: the engine takes the strides), the caller's stream waits for all of them.  Returns (timestep, rewards,
+        repeat_count) of the whole batch; the results do not depend on G."""
+        torch = self._torch
+        p0 = self.parts[0]
+        T = p0._check_rollout(p0._sequence_length(actions))
+        a = p0._pack_sequence(actions, self.num_envs)
+        with torch.cuda.device(self.device):
+            rewards = torch.empty((T, self.num_envs), dtype=torch.float64, device=self.device)
+        m = self.part_envs
+        for g in range(self.sub_batches):
+            a.record_stream(self._streams[g])
+            rewards.record_stream(self._streams[g])
+            self._enqueue(g, lambda g=g: self.parts[g]._rollout_packed(a[:, g * m:(g + 1) * m], rewards[:, g * m:(g + 1) * m]))
+        self._join()
+        return self._timestep(), rewards, self.repeat_count
 
     def random_action(self):
         torch = self._torch
