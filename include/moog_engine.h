@@ -889,6 +889,22 @@ int moog_engine_view_raster_path(moog_engine_t* e, int32_t view, int32_t* path);
 int moog_engine_add_table(moog_engine_t* e, const moog_table_t* table_desc, int32_t* table);
 int moog_engine_set_table_buffer(moog_engine_t* e, int32_t table, void* table_dev);
 int moog_engine_observe_tables(moog_engine_t* e, void* hip_stream);
+/* Rollout trajectories.  Replaces the n_steps moog_engine_step calls with a bound table that a planner makes to see the
+ * states a roll-out passes through (the reference's SimulationEnvironment steps one sim_step at a time and reads the state
+ * after each): moog_engine_set_table_trajectory binds, for table `table` of the handle, a device buffer of n_steps blocks of
+ * [n_envs][n_rows][n_cols] of the table's dtype, block j at traj_dev + j * step_elems elements (borrowed; aligned as for
+ * moog_engine_set_table_buffer; NULL unbinds).  The binding holds for the moog_engine_step_sequence calls that follow, each
+ * of at most as many steps as the buffer has blocks.  Such a call writes, from inside its one launch of the step kernel and
+ * from the record on chip, block j of env i right after env-step j of that env: exactly the bytes the table's own buffer would
+ * hold after a moog_engine_step call that took this env-step (the step that ends an episode included, as it leaves the
+ * record).  The blocks of the steps an env does not take -- those behind the step that ended its episode, every step of an
+ * env the call reset instead, on the in-place, reset-pool and late-reset paths alike -- hold zero bits in every column; the
+ * kernel writes them, the buffer needs no clearing.  step_elems above n_envs x n_rows x n_cols lets a sub-batch record into
+ * its slice of a whole-batch [n_steps][N][n_rows][n_cols] array in place.  A table may have a buffer, a trajectory, or both.
+ * moog_engine_step takes no trajectory, at any action repeat: it ignores the binding, as do moog_engine_reset and
+ * moog_engine_physics_only.  Limits: sprite tables only (no frames, segmentations, ray sensors or contacts per step).
+ * MOOG_E_INVALID: null engine, no such table, a misaligned buffer, step_elems < n_envs x n_rows x n_cols with a non-null buffer. */
+int moog_engine_set_table_trajectory(moog_engine_t* e, int32_t table, void* traj_dev, int64_t step_elems);
 
 /* Ray sensors.  Egocentric range readings for a state-based agent: how far, and to what, along each of n_rays directions from
  * one sprite.  The reference has no such observer (it leaves featurising to the caller, observers/raw_state.py:17-19).

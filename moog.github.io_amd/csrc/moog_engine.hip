@@ -78,10 +78,12 @@ struct RView {
 };
 
 // A sprite table of the engine (moog_engine_add_table): the kernel's descriptor, its rows on the device, and -- in desc.out --
-// the bound buffer (moog_engine_set_table_buffer), or null.
+// the bound buffer (moog_engine_set_table_buffer), or null.  `traj`: what the step kernel's recorder needs of the table (its
+// rows, its column ids) and -- in traj.out -- the trajectory bound for the sequences to come (moog_engine_set_table_trajectory).
 struct STable {
   StTable desc{};
   int32_t* d_rows = nullptr;
+  TrajTable traj{};
 };
 
 // A segmentation of the engine (moog_engine_add_segmentation): the raster state of a view of its size and modifier (always on
@@ -840,11 +842,13 @@ int moog_engine_create(const moog_program_t* prog, int32_t n_envs, int32_t devic
     if (rc) { free_engine(e); return rc; }
   }
   {
-    int (*const configure[12])(size_t) = {moog_configure_step_f3, moog_configure_step_f4, moog_configure_step_t3,
+    int (*const configure[18])(size_t) = {moog_configure_step_f3, moog_configure_step_f4, moog_configure_step_t3,
                                           moog_configure_step_t4, moog_configure_step_m3, moog_configure_step_m4,
                                           moog_configure_step_f3r, moog_configure_step_f4r, moog_configure_step_t3r,
-                                          moog_configure_step_t4r, moog_configure_step_m3r, moog_configure_step_m4r};
-    for (int v = 0; v < 12 && err == hipSuccess; ++v) err = (hipError_t)configure[v](e->step_lds);
+                                          moog_configure_step_t4r, moog_configure_step_m3r, moog_configure_step_m4r,
+                                          moog_configure_step_f3rt, moog_configure_step_f4rt, moog_configure_step_t3rt,
+                                          moog_configure_step_t4rt, moog_configure_step_m3rt, moog_configure_step_m4rt};
+    for (int v = 0; v < 18 && err == hipSuccess; ++v) err = (hipError_t)configure[v](e->step_lds);
   }
   {
     const StepVariant sv = step_variant_of(prog);
@@ -983,6 +987,7 @@ static KArgs make_args(moog_engine* e, const void* actions, const moog_inject_t*
   a.repeat = mode == MODE_STEP ? e->action_repeat : 1;
   a.repeat_count = mode == MODE_STEP ? e->repeat_count : nullptr;
   a.act_step_bytes = 0; a.reward_seq = nullptr; a.reward_seq_stride = 0;   // (moog_engine_step_sequence sets the three)
+  memset(a.traj, 0, sizeof a.traj);   // (... and the trajectories bound with moog_engine_set_table_trajectory: no other call records)
   a.xstack_off = e->xstack_off;
   a.watch = (mode == MODE_STEP) ? e->watch : nullptr; a.watch_off = e->watch_off;
   a.fops = e->d_fops; a.n_fops = e->n_fops;
@@ -1004,17 +1009,20 @@ static bool steps_specialised(const moog_engine* e) { return e->spec_launch && e
 
 static void launch_step(moog_engine* e, hipStream_t s, const KArgs& a) {
   // (the second six: the kernels with the action-repeat loop, for calls that take more than one env-step and for action
-  //  sequences, whose per-step rewards the one-step kernels do not write)
-  static const moog_step_launch_fn launch[12] = {moog_launch_step_f3, moog_launch_step_f4, moog_launch_step_t3,
+  //  sequences, whose per-step rewards the one-step kernels do not write; the third six: those with the trajectory recorder
+  //  as well, for sequences with a trajectory bound -- with a profiling word or a watcher set too: these are generic kernels)
+  static const moog_step_launch_fn launch[18] = {moog_launch_step_f3, moog_launch_step_f4, moog_launch_step_t3,
                                                  moog_launch_step_t4, moog_launch_step_m3, moog_launch_step_m4,
                                                  moog_launch_step_f3r, moog_launch_step_f4r, moog_launch_step_t3r,
-                                                 moog_launch_step_t4r, moog_launch_step_m3r, moog_launch_step_m4r};
+                                                 moog_launch_step_t4r, moog_launch_step_m3r, moog_launch_step_m4r,
+                                                 moog_launch_step_f3rt, moog_launch_step_f4rt, moog_launch_step_t3rt,
+                                                 moog_launch_step_t4rt, moog_launch_step_m3rt, moog_launch_step_m4rt};
   if (steps_specialised(e)) {
     e->spec_launch(e->n_envs, e->step_lds, s, &a);
     return;
   }
   const bool full = e->maze_kernel && !e->late_reset;
-  launch[((a.repeat > 1 || a.reward_seq) ? 6 : 0) + (full ? 4 : (e->dynamic_rules ? 2 : 0)) + (e->step_wps == 4 ? 1 : 0)](e->n_envs, e->step_lds, s, a);
+  launch[(a.traj[0].out ? 12 : (a.repeat > 1 || a.reward_seq) ? 6 : 0) + (full ? 4 : (e->dynamic_rules ? 2 : 0)) + (e->step_wps == 4 ? 1 : 0)](e->n_envs, e->step_lds, s, a);
 }
 
 // What the draw-record emitter needs (moog_draw_record.h): by value in the step kernel's and the derive kernel's arguments.
@@ -1319,6 +1327,9 @@ static int step_call(moog_engine* e, const void* actions_dev, int32_t n_steps, i
     a.act_step_bytes = act_step_bytes;
     a.reward_seq = rewards_dev;
     a.reward_seq_stride = reward_step_elems;
+    int n_traj = 0;   // (the tables with a trajectory first: the kernels stop at the first descriptor without a buffer)
+    for (int k = 0; k < e->n_tables; ++k)
+      if (e->tables[k].traj.out) a.traj[n_traj++] = e->tables[k].traj;
   }
   int rc;
   const bool emit = out && out->image && step_emits_draw(e);
@@ -1675,6 +1686,12 @@ int moog_engine_add_table(moog_engine_t* e, const moog_table_t* table_desc, int3
   HIPCHK(hipMemcpy(t.d_rows, rows, sizeof(int32_t) * (size_t)table_desc->n_rows, hipMemcpyHostToDevice));
   d.rows = t.d_rows;
   t.desc = d;
+  memset(&t.traj, 0, sizeof t.traj);
+  t.traj.rows = t.d_rows;
+  t.traj.n_rows = table_desc->n_rows;
+  t.traj.n_cols = (uint8_t)table_desc->n_cols;
+  t.traj.dtype = (uint8_t)table_desc->dtype;
+  for (int c = 0; c < table_desc->n_cols; ++c) t.traj.cols[c / 8] |= (uint64_t)(uint8_t)table_desc->cols[c] << (8 * (c % 8));
   *table = e->n_tables++;
   return MOOG_OK;
 }
@@ -1687,6 +1704,19 @@ int moog_engine_set_table_buffer(moog_engine_t* e, int32_t table, void* table_de
     return fail(MOOG_E_INVALID, "sprite table buffer must be aligned to its element type");
   e->n_bound_tables += (table_dev ? 1 : 0) - (d.out ? 1 : 0);
   d.out = table_dev;
+  return MOOG_OK;
+}
+
+int moog_engine_set_table_trajectory(moog_engine_t* e, int32_t table, void* traj_dev, int64_t step_elems) {
+  if (!e) return fail(MOOG_E_INVALID, "null engine");
+  if (table < 0 || table >= e->n_tables) return fail(MOOG_E_INVALID, "no such sprite table");
+  TrajTable& t = e->tables[table].traj;
+  if ((uintptr_t)traj_dev & (t.dtype == MOOG_TABLE_F16 ? 1u : 3u))
+    return fail(MOOG_E_INVALID, "sprite table trajectory must be aligned to its element type");
+  if (traj_dev && step_elems < (int64_t)e->n_envs * t.n_rows * (int64_t)t.n_cols)
+    return fail(MOOG_E_INVALID, "sprite table trajectory: step_elems is less than one step's block (n_envs x n_rows x n_cols)");
+  t.out = traj_dev;
+  t.step_elems = traj_dev ? step_elems : 0;
   return MOOG_OK;
 }
 

@@ -4,6 +4,7 @@
 #pragma once
 #include "moog_device.h"
 #include "moog_draw_record.h"   // the rasteriser's input, written where the record is on chip (step_env's epilogue)
+#include "moog_sprite_table.h"  // the sprite tables' conversions and column ids: the trajectory recorder writes the same tables
 
 // What the launch order of the next call sorts by (moog_sched_kernel): 0.6 x this call's cycles + 0.4 x the previous value.  An
 // env that was expensive lately tends to be expensive again (a pile of sprites in contact) even when one call in between was
@@ -112,6 +113,21 @@ __device__ inline void store_record(const Env& e, const HotLayout& h, const moog
   }
 }
 
+// One recorded table of a sequence's trajectory (moog_engine_set_table_trajectory): by value in the launch arguments, so
+// that the kernels read it with scalar loads and a specialised build needs no copy of it.  The column ids are bytes packed
+// into words: every access to the launch arguments keeps a constant index (an array indexed by the column loop would pin
+// the specialised kernels' copy of the arguments in scratch memory).
+struct TrajTable {
+  void* out;               // [n_steps] blocks of [n_envs][n_rows][n_cols] of dtype, step_elems elements apart; null: not used
+  const int32_t* rows;     // the table's device array: slot | layer << 16 per row (StTable::rows)
+  int64_t step_elems;      // elements between the blocks of two steps
+  uint64_t cols[(MOOG_MAX_TABLE_COLS + 7) / 8];   // column c's id (MOOG_TCOL_*): byte c % 8 of word c / 8
+  int32_t n_rows;
+  uint8_t n_cols, dtype;   // MOOG_TABLE_*
+};
+static_assert(sizeof(TrajTable) <= 64, "a trajectory descriptor is passed by value, once per table");
+static_assert(MOOG_TCOL_COUNT <= 256, "a column id is one byte of TrajTable::cols");
+
 // (the flattened force list KArgs::fops points to: moog_flatten_forces, moog_fops.h)
 struct KArgs {
   const moog_program_t* P;
@@ -167,6 +183,10 @@ struct KArgs {
   int64_t act_step_bytes;
   double* reward_seq;    // [repeat][...] or null
   int64_t reward_seq_stride;   // elements between the rows of two steps
+  // trajectory of a sequence (moog_engine_set_table_trajectory; read by the kernels with the recorder only, step_env<.., RECORD>): after step j of the
+  // call every table here gets the env's rows as they are then, at block j; the blocks of the steps an env does not take hold
+  // zero bits.  The tables in use come first: traj[0].out == null means that nothing is recorded.
+  TrajTable traj[MOOG_MAX_TABLES];
 };
 
 enum { MODE_STEP = 0, MODE_PHYSICS = 1, MODE_RESET_MASK = 2, MODE_FILL = 3 };
@@ -186,6 +206,72 @@ extern __shared__ __attribute__((aligned(16))) unsigned char moog_lds[];
 static_assert(MOOG_MAX_ACTION_REPEAT <= 64, "one lane per step of a sequence");
 __device__ __forceinline__ void reward_seq_zero(const KArgs& a, int env, int lane, int from) {
   if (a.reward_seq && lane >= from && lane < a.repeat) a.reward_seq[(long long)lane * a.reward_seq_stride + env] = 0.0;
+}
+
+// ---- trajectory recorder (moog_engine_set_table_trajectory) ---------------------------------------------------------------
+// Table k of the launch's trajectory, as scalars: every field of all four descriptors is loaded at its constant place in the
+// launch arguments and the k-th value selected (see TrajTable: no address may depend on k or on the column, and a local
+// copy of a descriptor -- a struct with an array in it -- stayed in scratch memory: 344 B instead of 48 in the plain kernel)
+struct TrajView {
+  void* out;
+  const int32_t* rows;
+  int64_t step_elems;
+  uint64_t c0, c1, c2;   // TrajTable::cols
+  int32_t n_rows, n_cols;
+  bool f16;
+};
+static_assert(MOOG_MAX_TABLES == 4 && MOOG_MAX_TABLE_COLS <= 24, "traj_pick selects among four descriptors of three column words");
+__device__ __forceinline__ TrajView traj_pick(const KArgs& a, int k) {
+  // (the values first, the selection after: a select between loaded values, never between addresses)
+  void* const o0 = a.traj[0].out; void* const o1 = a.traj[1].out; void* const o2 = a.traj[2].out; void* const o3 = a.traj[3].out;
+  const int32_t* const r0 = a.traj[0].rows; const int32_t* const r1 = a.traj[1].rows;
+  const int32_t* const r2 = a.traj[2].rows; const int32_t* const r3 = a.traj[3].rows;
+  const int64_t s0 = a.traj[0].step_elems, s1 = a.traj[1].step_elems, s2 = a.traj[2].step_elems, s3 = a.traj[3].step_elems;
+  const uint64_t a0 = a.traj[0].cols[0], a1 = a.traj[1].cols[0], a2 = a.traj[2].cols[0], a3 = a.traj[3].cols[0];
+  const uint64_t b0 = a.traj[0].cols[1], b1 = a.traj[1].cols[1], b2 = a.traj[2].cols[1], b3 = a.traj[3].cols[1];
+  const uint64_t d0 = a.traj[0].cols[2], d1 = a.traj[1].cols[2], d2 = a.traj[2].cols[2], d3 = a.traj[3].cols[2];
+  const int32_t n0 = a.traj[0].n_rows, n1 = a.traj[1].n_rows, n2 = a.traj[2].n_rows, n3 = a.traj[3].n_rows;
+  const int32_t m0 = a.traj[0].n_cols, m1 = a.traj[1].n_cols, m2 = a.traj[2].n_cols, m3 = a.traj[3].n_cols;
+  const int32_t t0 = a.traj[0].dtype, t1 = a.traj[1].dtype, t2 = a.traj[2].dtype, t3 = a.traj[3].dtype;
+#define MOOG_TRAJ_SEL(x0, x1, x2, x3) (k == 0 ? (x0) : (k == 1 ? (x1) : (k == 2 ? (x2) : (x3))))
+  TrajView v;
+  v.out = MOOG_TRAJ_SEL(o0, o1, o2, o3);
+  v.rows = MOOG_TRAJ_SEL(r0, r1, r2, r3);
+  v.step_elems = MOOG_TRAJ_SEL(s0, s1, s2, s3);
+  v.c0 = MOOG_TRAJ_SEL(a0, a1, a2, a3);
+  v.c1 = MOOG_TRAJ_SEL(b0, b1, b2, b3);
+  v.c2 = MOOG_TRAJ_SEL(d0, d1, d2, d3);
+  v.n_rows = MOOG_TRAJ_SEL(n0, n1, n2, n3);
+  v.n_cols = MOOG_TRAJ_SEL(m0, m1, m2, m3);
+  v.f16 = MOOG_TRAJ_SEL(t0, t1, t2, t3) == MOOG_TABLE_F16;
+#undef MOOG_TRAJ_SEL
+  return v;
+}
+__device__ __forceinline__ int traj_col(const TrajView& t, int c) {
+  const uint64_t w = c < 8 ? t.c0 : (c < 16 ? t.c1 : t.c2);
+  return (int)((w >> ((c & 7) * 8)) & 0xffu);
+}
+
+// Action sequence: the trajectory blocks of the steps from `from` on, which the env does not take, are zero bits -- written
+// here, by the env's own wavefront, for the reason reward_seq_zero gives (a sub-batch writes only its own envs' part of a
+// whole-batch tensor, and nothing orders the sub-batches' streams: the host cannot clear it)
+__device__ __forceinline__ void traj_zero(const KArgs& a, int env, int lane, int from) {
+  if (!a.traj[0].out) return;
+  for (int k = 0; k < MOOG_MAX_TABLES; ++k) {
+    const TrajView t = traj_pick(a, k);
+    if (!t.out) break;
+    const int per_env = t.n_rows * t.n_cols;
+    for (int j = from; j < a.repeat; ++j) {
+      const long long base = (long long)j * t.step_elems + (long long)env * per_env;
+      if (t.f16) {   // (2-byte stores: an env's block may start on an odd half-word)
+        uint16_t* o = static_cast<uint16_t*>(t.out) + base;
+        for (int i = lane; i < per_env; i += 64) o[i] = 0;
+      } else {
+        uint32_t* o = static_cast<uint32_t*>(t.out) + base;
+        for (int i = lane; i < per_env; i += 64) o[i] = 0u;
+      }
+    }
+  }
 }
 
 // lds: this wave's record area (the whole dynamic LDS of a one-wave workgroup)
@@ -265,6 +351,62 @@ __device__ __forceinline__ void emit_draw_record(const Env& e, const KArgs& a, i
     a.step_type[env] = (int32_t)(clock64() - t_emit);
     if (a.discount) a.discount[env] = (double)(clk[1] - clk[0]) + 65536.0 * (double)(clk[2] - clk[1]);
     if (a.reward) a.reward[env] = (double)(clk[3] - clk[2]) + 65536.0 * (double)(clk[4] - clk[3]);
+  }
+}
+
+// The env's rows of every recorded table after env-step `step` of a sequence, from the record where the step left it: LDS
+// (EF / EQ at the hot layout's offsets) and, for colours, opacities and shape ids, wherever bind_env says they live (COL /
+// OPAC / SHAPEID: the writers fence their stores, wave_global_fence).  Each element is what moog_st_element gives for the
+// record after a step() call that took this env-step: a dead slot's row is zero, one rounding (moog_sprite_table.h).
+// Mapping: a lane per row, the columns in a wave-uniform loop -- the column's id is a scalar, the switch a scalar branch and
+// no lane divides anything; a wave's stores are n_cols elements apart (DESIGN 3.1 "Rollout trajectories").
+__device__ __forceinline__ void traj_record(const Env& e, const KArgs& a, int env, int step) {
+  if (!a.traj[0].out) return;   // (the caller has passed a wsync() since the step's last store to the record)
+  for (int k = 0; k < MOOG_MAX_TABLES; ++k) {
+    const TrajView t = traj_pick(a, k);
+    if (!t.out) break;
+    const int nr = t.n_rows, nc = t.n_cols;
+    const bool f16 = t.f16;
+    const long long base = (long long)step * t.step_elems + (long long)env * (nr * nc);
+    for (int r0 = 0; r0 < nr; r0 += 64) {
+      const int r = r0 + e.lane;
+      const bool in = r < nr;
+      const int32_t rw = in ? t.rows[r] : 0;
+      const int s = rw & 0xffff;
+      const bool live = in && (FLAGS(s) & MOOG_F_ALIVE) != 0;
+      for (int c = 0; c < nc; ++c) {
+        double v = 0.0;
+        switch (traj_col(t, c)) {   // (MOOG_TCOL_*: the sources moog_st_describe names)
+          case MOOG_TCOL_ALIVE: v = 1.0; break;
+          case MOOG_TCOL_LAYER: v = (double)(rw >> 16); break;
+          case MOOG_TCOL_X: v = PX(s); break;
+          case MOOG_TCOL_Y: v = PY(s); break;
+          case MOOG_TCOL_X_VEL: v = VELX(s); break;
+          case MOOG_TCOL_Y_VEL: v = VELY(s); break;
+          case MOOG_TCOL_ANGLE: v = ANG(s); break;
+          case MOOG_TCOL_ANGLE_VEL: v = ANGV(s); break;
+          case MOOG_TCOL_MASS: v = MASS(s); break;
+          case MOOG_TCOL_C0: v = COL(s, 0); break;
+          case MOOG_TCOL_C1: v = COL(s, 1); break;
+          case MOOG_TCOL_C2: v = COL(s, 2); break;
+          case MOOG_TCOL_SCALE: if (EL(e).o_scale >= 0) v = SCALE(s); break;   // (a table with this column needs the field: moog_st_describe)
+          case MOOG_TCOL_ASPECT: if (EL(e).o_aspect >= 0) v = ASPECT(s); break;
+          case MOOG_TCOL_OPACITY: v = (double)OPAC(s); break;
+          case MOOG_TCOL_SHAPE_ID: v = (double)SHAPEID(s); break;
+          case MOOG_TCOL_N_VERTICES: v = (double)NV(s); break;
+          default: break;
+        }
+        const uint64_t b = moog_st_bits_of(v);
+        const long long at = base + (long long)r * nc + c;
+        if (f16) {
+          const uint32_t h = live ? moog_st_f64_to_f16_bits(b) : 0u;
+          if (in) static_cast<uint16_t*>(t.out)[at] = (uint16_t)h;
+        } else {
+          const uint32_t w = live ? moog_st_f64_to_f32_bits(b) : 0u;
+          if (in) static_cast<uint32_t*>(t.out)[at] = w;
+        }
+      }
+    }
   }
 }
 
@@ -635,8 +777,13 @@ __device__ __forceinline__ double uni_f64(double x) {
 // REPEAT = the instantiation carries the action-repeat loop (moog_engine_set_action_repeat with k > 1).  The loop in the
 // one-step kernels cost the headline 2.3 % at k = 1 (registers of the collision recursion went to scratch:
 // profiles/action_repeat.txt), so those compile the body as the straight line it was and the loop has kernels of its own.
-template <bool DYN, bool REPEAT>
+// RECORD = the instantiation also carries the trajectory recorder (moog_engine_set_table_trajectory): kernels of their own beside
+// the REPEAT ones, launched only when a trajectory is bound.  Inside the REPEAT kernels, behind a wave-uniform test, the
+// recorder took the plain one's frame from 48 B / 17 spilled VGPRs to 136 B / 24 -- the sequences and repeats that record
+// nothing would have paid for it (DESIGN 3.1 "Rollout trajectories"); this way they keep the code they had.
+template <bool DYN, bool REPEAT, bool RECORD = false>
 __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned char* lds, const int lane) {
+  static_assert(REPEAT || !RECORD, "the recorder sits in the repeat loop");
   const long long t_sched = a.cost ? clock64() : 0;
   int32_t* gq = a.i32 + (size_t)env * a.L.i32_per_env;
   Env e;
@@ -656,6 +803,7 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
         // as it is; the full reset kernel, launched behind this one, opens its episode and releases the pool's lock.
         if (e.lane == 0) { a.late_mask[env] = 1; if (a.repeat_count) a.repeat_count[env] = 0; }
         if constexpr (REPEAT) reward_seq_zero(a, env, e.lane, 0);
+        if constexpr (RECORD) traj_zero(a, env, e.lane, 0);
         return;
       }
       env_reset<DYN>(e);
@@ -675,6 +823,7 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
 #endif
     }
     if constexpr (REPEAT) reward_seq_zero(a, env, e.lane, 0);
+    if constexpr (RECORD) traj_zero(a, env, e.lane, 0);
     emit_draw_record(e, a, env);   // (before the record's stores: a wave waits once for its stores to drain, at its end)
     store_record(e, a.H, a.L, gf, gq, a.fault_flag);
     if (DYN && held) pool_release(a, env, e.lane);
@@ -745,6 +894,7 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
     if constexpr (REPEAT) {
       if (a.reward_seq && e.lane == 0) a.reward_seq[(long long)done * a.reward_seq_stride + env] = rj;
     }
+    if constexpr (RECORD) traj_record(e, a, env, done);   // (before the exit test: the step that ends the episode is recorded as it leaves the record)
     if (!REPEAT || reps <= 1) { rsum = rj; done = 1; break; }   // (a single step: its reward and flag as they are)
     sr = uni(sr);
     rj = uni_f64(rj);
@@ -759,6 +909,7 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
     if (a.repeat_count) a.repeat_count[env] = done;
   }
   if constexpr (REPEAT) reward_seq_zero(a, env, e.lane, done);
+  if constexpr (RECORD) traj_zero(a, env, e.lane, done);
   SEC(e, SEC_STORE);
   emit_draw_record(e, a, env);   // (before the record's stores: a wave waits once for its stores to drain, at its end)
   store_record(e, a.H, a.L, gf, gq, a.fault_flag);
@@ -772,7 +923,7 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
   }
 }
 
-template <bool DYN, int WPS, int VARIANT, bool REPEAT>   // VARIANT only names the instantiation (one per translation unit)
+template <bool DYN, int WPS, int VARIANT, bool REPEAT, bool RECORD = false>   // VARIANT only names the instantiation (one per translation unit)
 // Every device function must end up inlined into this kernel: the env's descriptor (`Env`: pointers and the layout's offsets)
 // has to live in registers.  One function left out of line takes it by reference through scratch memory, ~1000 cycles per
 // access: round 4 measured this kernel at 1270 instead of 800 us the day the inliner's cost model left apply_physics out
@@ -813,7 +964,7 @@ __global__ __launch_bounds__(MOOG_STEP_THREADS, WPS) void moog_step_kernel(KArgs
     a.H = hot_layout(L);
   }
 #endif
-  step_env<DYN, REPEAT>(a, env, moog_lds, (int)threadIdx.x);
+  step_env<DYN, REPEAT, RECORD>(a, env, moog_lds, (int)threadIdx.x);
 #ifdef MOOG_WATCH
   if (a.watch && threadIdx.x == 0) { int32_t* w = reinterpret_cast<int32_t*>(__builtin_assume_aligned(moog_lds + a.watch_off, 16)); __hip_atomic_store(w + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 #endif
@@ -821,7 +972,8 @@ __global__ __launch_bounds__(MOOG_STEP_THREADS, WPS) void moog_step_kernel(KArgs
 
 
 // ---- launch functions (one translation unit each, so that they compile in parallel) ------------------
-// variant = (dynamic rules ? 2 : 0) + (waves per SIMD == 4 ? 1 : 0); the ...r functions: the kernels with the action-repeat loop
+// variant = (dynamic rules ? 2 : 0) + (waves per SIMD == 4 ? 1 : 0); the ...r functions: the kernels with the action-repeat loop;
+// the ...rt functions: those with the trajectory recorder as well
 typedef void (*moog_step_launch_fn)(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 void moog_launch_step_f3(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 void moog_launch_step_f4(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
@@ -835,6 +987,12 @@ void moog_launch_step_t3r(int n_envs, size_t lds, hipStream_t s, const KArgs& a)
 void moog_launch_step_t4r(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 void moog_launch_step_m3r(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 void moog_launch_step_m4r(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
+void moog_launch_step_f3rt(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
+void moog_launch_step_f4rt(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
+void moog_launch_step_t3rt(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
+void moog_launch_step_t4rt(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
+void moog_launch_step_m3rt(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
+void moog_launch_step_m4rt(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 int moog_configure_step_f3(size_t lds);
 int moog_configure_step_f4(size_t lds);
 int moog_configure_step_t3(size_t lds);
@@ -847,6 +1005,12 @@ int moog_configure_step_t3r(size_t lds);
 int moog_configure_step_t4r(size_t lds);
 int moog_configure_step_m3r(size_t lds);
 int moog_configure_step_m4r(size_t lds);
+int moog_configure_step_f3rt(size_t lds);
+int moog_configure_step_f4rt(size_t lds);
+int moog_configure_step_t3rt(size_t lds);
+int moog_configure_step_t4rt(size_t lds);
+int moog_configure_step_m3rt(size_t lds);
+int moog_configure_step_m4rt(size_t lds);
 void moog_launch_reset_plain(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 void moog_launch_reset_full(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 int moog_configure_reset_plain(size_t lds);

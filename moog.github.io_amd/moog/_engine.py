@@ -26,7 +26,7 @@ SYMBOLS = (
     'moog_engine_add_sensor', 'moog_engine_set_sensor_buffer', 'moog_engine_observe_sensors',
     'moog_engine_add_contacts', 'moog_engine_set_contacts_buffer', 'moog_engine_observe_contacts',
     'moog_engine_add_segmentation', 'moog_engine_set_segmentation_image',
-    'moog_engine_step_sequence',
+    'moog_engine_step_sequence', 'moog_engine_set_table_trajectory',
 )
 
 _LIB = None
@@ -86,6 +86,7 @@ def load_library(path=None):
     lib.moog_engine_view_raster_path.argtypes = [vp, i32, ctypes.POINTER(i32)]
     lib.moog_engine_add_table.argtypes = [vp, ctypes.POINTER(_abi.Table), ctypes.POINTER(i32)]
     lib.moog_engine_set_table_buffer.argtypes = [vp, i32, vp]
+    lib.moog_engine_set_table_trajectory.argtypes = [vp, i32, vp, i64]
     lib.moog_engine_observe_tables.argtypes = [vp, vp]
     lib.moog_engine_add_sensor.argtypes = [vp, ctypes.POINTER(_abi.Sensor), ctypes.POINTER(i32)]
     lib.moog_engine_set_sensor_buffer.argtypes = [vp, i32, vp]

@@ -918,7 +918,32 @@ class BatchedEnvironment(object):
                                       'available: set_action_repeat(1) first' % self._action_repeat)
         return self._check_action_repeat(T)   # (T env-steps inside one launch: what a repeat of T cannot do, this cannot either)
 
-    def rollout(self, actions):
+    def _check_record(self, record):
+        """rollout()'s `record` as a list of SpriteTable keys, or the reason it cannot be recorded (no device needed)."""
+        from .observers import sprite_table
+        keys = [record] if isinstance(record, str) else list(record)
+        if not keys:
+            raise ValueError('rollout: record is empty: name at least one SpriteTable observer of the config (or pass None)')
+        for key in keys:
+            if key not in self.observers:
+                raise KeyError('rollout: record names %r, which is not an observer of this config (%s)'
+                               % (key, sorted(self.observers, key=str)))
+            if not isinstance(self.observers[key], sprite_table.SpriteTable):
+                raise TypeError('rollout: record names %r, a %s: only SpriteTable observers are recorded per step'
+                                % (key, type(self.observers[key]).__name__))
+        if len(set(keys)) != len(keys):
+            raise ValueError('rollout: record names a key twice: %s' % (keys,))
+        return keys
+
+    def _new_trajectory(self, keys, T, n=None):
+        """{key: [T, n, rows, columns] of the table's dtype}, uninitialised: the step kernel writes every element."""
+        torch = self._torch
+        n = self.num_envs if n is None else n
+        with torch.cuda.device(self.device):
+            return {key: torch.empty((T, n) + tuple(self.tables[key].shape[1:]), dtype=self.tables[key].dtype, device=self.device)
+                    for key in keys}
+
+    def rollout(self, actions, record=None):
         """Open loop: T env-steps with T different actions inside one launch of the step kernel, no observation in between
         (a planner's roll-out: random shooting, CEM / MPC, the leaves of a tree search; with snapshot() / restore(), the
         reference's SimulationEnvironment).  actions: [T, N, 2] (Joystick; float32 stays float32, as in step()), [T, N]
@@ -929,22 +954,45 @@ class BatchedEnvironment(object):
           count     `repeat_count`, int32 [N]: the env-steps each env took (0: the call reset the env, a FIRST timestep)
           timestep  what a step() at action_repeat=T returns: the rewards' sum in step order, the step_type / discount of
                     the last step taken, the observations after it.
-        The state after the call is, bit for bit, the state after count single step() calls with the same actions."""
-        T = self._check_rollout(self._sequence_length(actions))   # (refusals first: they need no device)
+        The state after the call is, bit for bit, the state after count single step() calls with the same actions.
+        record: the key of a SpriteTable observer of the config, or a list / tuple of keys: the states in between.  The call
+        then returns (timestep, rewards, count, trajectory), trajectory = {key: a fresh tensor [T, N, rows, columns] of the
+        table's dtype}: trajectory[key][j, e] holds exactly what tables[key][e] would hold after a step() call that took
+        env-step j of env e (the step that ended an episode included), and zero bits -- `alive` too -- for the steps env e
+        did not take.  The step kernel writes it from the record on chip (moog_engine_set_table_trajectory)."""
+        keys = None if record is None else self._check_record(record)   # (refusals first: they need no device)
+        T = self._check_rollout(self._sequence_length(actions))
         torch = self._torch
         a = self._pack_sequence(actions)
         with torch.cuda.device(self.device):
             rewards = torch.empty((T, self.num_envs), dtype=torch.float64, device=self.device)
-        ts = self._rollout_packed(a, rewards)
-        return ts, rewards, self.repeat_count
+        if keys is None:
+            ts = self._rollout_packed(a, rewards)
+            return ts, rewards, self.repeat_count
+        traj = self._new_trajectory(keys, T)
+        ts = self._rollout_packed(a, rewards, traj)
+        return ts, rewards, self.repeat_count, traj
 
-    def _rollout_packed(self, a, rewards):
+    def _bind_trajectory(self, traj):
+        """Binds (or, with None for a tensor, unbinds) the trajectory tensors of the sequences to come."""
+        for key, t in traj.items():
+            _engine.check(self._lib, self._lib.moog_engine_set_table_trajectory(
+                self._handle, self._table_index[key], ctypes.c_void_p(t.data_ptr() if t is not None else None),
+                t.stride(0) if t is not None else 0))
+
+    def _rollout_packed(self, a, rewards, traj=None):
         """rollout() on packed actions [T, n, ...] and a reward tensor [T, n] of the caller's, either one possibly a slice of
-        a whole batch's (rows further apart than their length: the engine takes the two strides)."""
+        a whole batch's (rows further apart than their length: the engine takes the two strides).  traj: None, or {SpriteTable
+        key: [T, n, rows, columns]} of the caller's, likewise possibly slices (the blocks of two steps further apart than n
+        envs' rows): recorded by this call only -- the tensors are bound before it and unbound behind it."""
         torch = self._torch
         T = self._check_rollout(int(a.shape[0]))
         assert a.shape[1] == self.num_envs and a[0].is_contiguous(), (tuple(a.shape), a.stride())
         assert tuple(rewards.shape) == (T, self.num_envs) and rewards.dtype == torch.float64 and rewards.stride(1) == 1
+        for key, t in (traj or {}).items():
+            own = self.tables[key]
+            assert tuple(t.shape) == (T, self.num_envs) + tuple(own.shape[1:]) and t.dtype == own.dtype, (key, tuple(t.shape), t.dtype)
+            assert t[0].is_contiguous() and t.stride(0) >= t[0].numel(), (key, t.stride())   # (the inner three dimensions)
         self._poll_faults()
         if a.dtype != torch.int32 and not self._composite:
             f32 = a.dtype == torch.float32
@@ -952,11 +1000,17 @@ class BatchedEnvironment(object):
                 _engine.check(self._lib, self._lib.moog_engine_set_action_dtype(self._handle, 1 if f32 else 0))
                 self._action_f32 = f32
         self._step_host_rules()   # (T == 1: _check_rollout refuses host-side rules beyond that)
-        with torch.cuda.device(self.device):
-            _engine.check(self._lib, self._lib.moog_engine_step_sequence(
-                self._handle, ctypes.c_void_p(a.data_ptr()), T, a.stride(0) * a.element_size(),
-                ctypes.c_void_p(rewards.data_ptr()), rewards.stride(0), None,
-                ctypes.byref(self._out if self._color_fn is None else self._out_noimg), self._stream()))
+        if traj:
+            self._bind_trajectory(traj)
+        try:
+            with torch.cuda.device(self.device):
+                _engine.check(self._lib, self._lib.moog_engine_step_sequence(
+                    self._handle, ctypes.c_void_p(a.data_ptr()), T, a.stride(0) * a.element_size(),
+                    ctypes.c_void_p(rewards.data_ptr()), rewards.stride(0), None,
+                    ctypes.byref(self._out if self._color_fn is None else self._out_noimg), self._stream()))
+        finally:
+            if traj:   # (a later rollout() without `record` must not write to this call's tensors)
+                self._bind_trajectory(dict.fromkeys(traj))
         if self._color_fn is not None:
             self._render_with_colors()
         self._last_action = a
@@ -1351,24 +1405,35 @@ class SubBatchedEnvironment(object):
         self._join()
         return self._timestep()
 
-    def rollout(self, actions):
+    def rollout(self, actions, record=None):
         """BatchedEnvironment.rollout of the whole batch, synchronous: the actions are packed once, every sub-batch runs its
         [T, num_envs / G, ...] slice of them on its own stream and writes its slice of one [T, num_envs] reward tensor (no
         copies: the engine takes the strides), the caller's stream waits for all of them.  Returns (timestep, rewards,
-        repeat_count) of the whole batch; the results do not depend on G."""
+        repeat_count) of the whole batch; the results do not depend on G.  record: as BatchedEnvironment.rollout -- one
+        [T, num_envs, rows, columns] tensor per key, sub-batch g recording into [:, g m:(g + 1) m] of it."""
         torch = self._torch
         p0 = self.parts[0]
+        keys = None if record is None else p0._check_record(record)
         T = p0._check_rollout(p0._sequence_length(actions))
         a = p0._pack_sequence(actions, self.num_envs)
         with torch.cuda.device(self.device):
             rewards = torch.empty((T, self.num_envs), dtype=torch.float64, device=self.device)
+        traj = None if keys is None else p0._new_trajectory(keys, T, self.num_envs)
         m = self.part_envs
         for g in range(self.sub_batches):
             a.record_stream(self._streams[g])
             rewards.record_stream(self._streams[g])
-            self._enqueue(g, lambda g=g: self.parts[g]._rollout_packed(a[:, g * m:(g + 1) * m], rewards[:, g * m:(g + 1) * m]))
+            part = None
+            if traj is not None:
+                for t in traj.values():
+                    t.record_stream(self._streams[g])
+                part = {key: t[:, g * m:(g + 1) * m] for key, t in traj.items()}
+            self._enqueue(g, lambda g=g, part=part: self.parts[g]._rollout_packed(
+                a[:, g * m:(g + 1) * m], rewards[:, g * m:(g + 1) * m], part))
         self._join()
-        return self._timestep(), rewards, self.repeat_count
+        if traj is None:
+            return self._timestep(), rewards, self.repeat_count
+        return self._timestep(), rewards, self.repeat_count, traj
 
     def random_action(self):
         torch = self._torch
