@@ -222,10 +222,16 @@ __device__ __forceinline__ double norm2(double x, double y) { return sqrt(x * x 
 __device__ __forceinline__ double npdot2(double a0, double a1, double b0, double b1) { return fma(a1, b1, a0 * b0); }
 __device__ __forceinline__ double npnorm(double x, double y) { return sqrt(fma(y, y, x * x)); }
 
-// sin / cos of the small per-substep rotation angles (|th| = |angle_vel| / K, typically
-// < 0.01 rad).  For |th| < 2^-5 the Taylor series through th^9 / th^8 is accurate to
-// below one ulp (next terms < 1e-22), i.e. as good as the library routines without
-// their argument reduction; larger angles use the library.
+// sin / cos of the per-substep rotation angles (|th| = |angle_vel| / K).  For |th| < 2^-5 the
+// Taylor series through th^9 / th^8 is accurate to below one ulp (next terms < 1e-22), i.e. as
+// good as the library routines without their argument reduction; larger angles use the library.
+// Small angles are NOT the rule: a reset draws |angle_vel| <= 0.05 on the headline, but contacts
+// spin the sprites up (CPU oracle, colliding_predators_32, 512 envs: median |angle_vel| 0.20 at
+// step 25, 37 % / 20 % / 8 % of the live sprites at or above the threshold at steps 25 / 100 / 200,
+// at least one such sprite in 93 - 100 % of the envs), and a wavefront runs the library branch as
+// soon as one lane is there.  That branch is ten times the Taylor one (compiled alone: 38 of 389
+// instructions are the series; the library's sin and cos reduce their argument separately), so
+// callers whose lanes hold copies of a scalar share a pass (relative_motion_matrix).
 __device__ __forceinline__ void sincos_small(double th, double* s, double* c) {
   if (fabs(th) < 0.03125) {
     double x2 = th * th;
@@ -1010,14 +1016,29 @@ __device__ inline void compose(double o[6], const double s[6], const double f[6]
   double r5 = (s[3] * f[2] + s[4] * f[5]) + s[5];
   o[0] = r0; o[1] = r1; o[2] = r2; o[3] = r3; o[4] = r4; o[5] = r5;
 }
-__device__ inline void rot_around(double m[6], double x, double y, double th) {
-  double a, b;
-  sincos_small(th, &b, &a);
+// the rotation by the angle whose cosine / sine are a / b around (x, y)
+__device__ __forceinline__ void rot_around(double m[6], double x, double y, double a, double b) {
   m[0] = a; m[1] = -b; m[2] = (a * (-x) - b * (-y)) + x;
   m[3] = b; m[4] = a; m[5] = (b * (-x) + a * (-y)) + y;
 }
 
-// collisions.py:62-98
+// collisions.py:62-98.  Called by all 64 lanes, and lanes l and l ^ 16 with the same (ps, as): the whole wavefront in
+// directed_collision_vectors, each half of it in directed_collision_vectors_pair.  Every lane needs the sine and cosine of both
+// angles and the lanes of a pair are copies of each other, so the two evaluations run as one: the lanes with bit 4 clear take
+// th0, the others th1, and an exchange with lane ^ 16 gives each lane the pair it did not compute.  A lane's sincos_small
+// depends on its own argument alone (NaN and the infinities included: the library branch, as before), so the four values are
+// those of two calls in a row, bit for bit; what is saved is the second pass through the library branch, which a wavefront
+// takes whenever one lane's angle is at or above 2^-5 (see sincos_small).  Debug bit 2048 selects the two calls in a row on the
+// generic kernels (not in a -DMOOG_PROFILE build: like 512 and 1024 the bit lies among those of the section selector, which
+// EDBG masks there, so `heavy_bench.py --sections` always times the one-pass form); a specialised build carries no switch.
+// The one-step kernels alone take the one-pass form.  The kernels with the action-repeat loop (a unit holds one kernel:
+// MOOG_STEP_REPEAT, MOOG_SPEC_KERNEL >= 1) keep the two calls: with the one-pass form their frames grew (the headline's
+// specialised repeat kernel 36 -> 52 B, generic f3r 48 -> 64 B) and the repeat-4 call of the headline was 1.4 % slower.
+#if (defined(MOOG_STEP_REPEAT) && MOOG_STEP_REPEAT) || (defined(MOOG_SPEC_KERNEL) && MOOG_SPEC_KERNEL >= 1)
+#define MOOG_MATRIX_ONE_PASS 0
+#else
+#define MOOG_MATRIX_ONE_PASS 1
+#endif
 __device__ inline void relative_motion_matrix(const Env& e, int ps, int as, double dt, double m[6]) {
   double th0, tx0, ty0, th1, tx1, ty1;
   float dtf = (float)dt;
@@ -1033,8 +1054,20 @@ __device__ inline void relative_motion_matrix(const Env& e, int ps, int as, doub
     tx1 = (double)((float)VELX(as) * dtf); ty1 = (double)((float)VELY(as) * dtf);
   } else { tx1 = VELX(as) * dt; ty1 = VELY(as) * dt; }
   double A[6], B[6] = {1, 0, tx0, 0, 1, ty0}, C[6], D[6] = {1, 0, tx1, 0, 1, ty1};
-  rot_around(A, PX(ps), PY(ps), th0);
-  rot_around(C, PX(as), PY(as), th1);
+  double a0, b0, a1, b1;   // cos / sin of th0, of th1
+  if (!MOOG_MATRIX_ONE_PASS || (EDBG(e) & 2048)) {
+    sincos_small(th0, &b0, &a0);
+    sincos_small(th1, &b1, &a1);
+  } else {
+    const bool second = (e.lane & 16) != 0;
+    double a, b;
+    sincos_small(second ? th1 : th0, &b, &a);
+    const double ao = shfl_d(a, e.lane ^ 16), bo = shfl_d(b, e.lane ^ 16);
+    a0 = second ? ao : a; b0 = second ? bo : b;
+    a1 = second ? a : ao; b1 = second ? b : bo;
+  }
+  rot_around(A, PX(ps), PY(ps), a0, b0);
+  rot_around(C, PX(as), PY(as), a1, b1);
   compose(m, B, A);
   compose(m, C, m);
   compose(m, D, m);
