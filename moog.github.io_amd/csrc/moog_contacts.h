@@ -49,8 +49,8 @@
 //      fly, stopping at the first hit.
 // The result is a pure function of the record: chunk size, grouping and drain order only decide when a bit is set.
 //
-// The host model needs the cross-lane steps too: as in moog_ray_sensor.h the wave function is written over a few macros that
-// make a "for every lane" block the thread's own lane on the device and a loop over 64 on the host, and a ballot a loop.
+// The host model needs the cross-lane steps too: as in moog_ray_sensor.h the wave function is written over the lane model of
+// moog_wave_model.h.
 #ifndef MOOG_CONTACTS_H_
 #define MOOG_CONTACTS_H_
 
@@ -60,10 +60,10 @@
 #include <string.h>
 
 #include "moog_sprite_table.h"
+#include "moog_wave_model.h"
 
-#define MOOG_CT_LANES 64
 #define MOOG_CT_GROUP 16                                   // lanes of one candidate pair in the narrow phase
-#define MOOG_CT_GROUPS (MOOG_CT_LANES / MOOG_CT_GROUP)
+#define MOOG_CT_GROUPS (MOOG_WAVE_LANES / MOOG_CT_GROUP)
 #define MOOG_CT_CHUNK 256                                  // candidates held in LDS at a time
 #define MOOG_CT_MAXV 128                                   // vertices of one polygon, at most (the engine's limit)
 #define MOOG_CT_MARGIN 1e-5
@@ -323,31 +323,6 @@ MOOG_ST_HD uint32_t moog_ct_four(const CtObs& s, const CtLds& l, uint32_t k) {
 }
 
 // ---- the wave function -------------------------------------------------------------------------------------------------
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MOOG_CT_NP 1
-#define MOOG_CT_EACH_LANE for (int lane = tid, once_ = 1; once_; once_ = 0)
-#define MOOG_CT_P 0
-#define MOOG_CT_SYNC() __syncthreads()
-#define MOOG_CT_BALLOT(arr) ((uint64_t)__ballot((arr)[0] != 0))
-#else
-#define MOOG_CT_NP MOOG_CT_LANES
-#define MOOG_CT_EACH_LANE for (int lane = 0; lane < MOOG_CT_LANES; ++lane)
-#define MOOG_CT_P lane
-#define MOOG_CT_SYNC() (void)tid
-static inline uint64_t moog_ct_host_ballot(const int32_t* v) {
-  uint64_t m = 0;
-  for (int k = 0; k < MOOG_CT_LANES; ++k) if (v[k]) m |= 1ull << k;
-  return m;
-}
-#define MOOG_CT_BALLOT(arr) moog_ct_host_ballot(arr)
-#endif
-MOOG_ST_HD int moog_ct_popc(uint64_t m) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __popcll(m);
-#else
-  return __builtin_popcountll(m);
-#endif
-}
 // the 16 bits of a ballot that belong to the group of `lane`
 MOOG_ST_HD uint32_t moog_ct_gbits(uint64_t m, int lane) { return (uint32_t)(m >> (lane & ~(MOOG_CT_GROUP - 1))) & 0xffffu; }
 
@@ -356,13 +331,13 @@ MOOG_ST_HD uint32_t moog_ct_gbits(uint64_t m, int lane) { return (uint32_t)(m >>
 // leaves with the same res (0 / 1) and proper.  A group's lanes may differ only between two ballots.
 MOOG_ST_HD void moog_ct_narrow(const CtArgs& a, const CtObs& s, const double* f, const CtLds& l, int tid, const int32_t* act,
                                const int32_t* ra, const int32_t* rb, int32_t* res, int32_t* proper) {
-  int32_t live[MOOG_CT_NP], na[MOOG_CT_NP], nb[MOOG_CT_NP], ca[MOOG_CT_NP], cb[MOOG_CT_NP], par[MOOG_CT_NP];
-  int32_t f1[MOOG_CT_NP], f2[MOOG_CT_NP], f3[MOOG_CT_NP];
-  const double* va[MOOG_CT_NP];
-  const double* vb[MOOG_CT_NP];
+  int32_t live[MOOG_WAVE_NP], na[MOOG_WAVE_NP], nb[MOOG_WAVE_NP], ca[MOOG_WAVE_NP], cb[MOOG_WAVE_NP], par[MOOG_WAVE_NP];
+  int32_t f1[MOOG_WAVE_NP], f2[MOOG_WAVE_NP], f3[MOOG_WAVE_NP];
+  const double* va[MOOG_WAVE_NP];
+  const double* vb[MOOG_WAVE_NP];
   // the empty-path rule; a polygon without a vertex
-  MOOG_CT_EACH_LANE {
-    const int P = MOOG_CT_P;
+  MOOG_WAVE_EACH_LANE {
+    const int P = MOOG_WAVE_P;
     res[P] = 0; proper[P] = 1; par[P] = 0; ca[P] = cb[P] = 0; na[P] = nb[P] = 0; va[P] = vb[P] = f;
     live[P] = act[P];
     if (act[P]) {
@@ -380,8 +355,8 @@ MOOG_ST_HD void moog_ct_narrow(const CtArgs& a, const CtObs& s, const double* f,
   }
   // the edges of a that reach b's DOP, and those of b that reach a's, compacted per group: 16 edges of each a pass
   for (int32_t k0 = 0; k0 < MOOG_CT_MAXV; k0 += MOOG_CT_GROUP) {
-    MOOG_CT_EACH_LANE {
-      const int P = MOOG_CT_P;
+    MOOG_WAVE_EACH_LANE {
+      const int P = MOOG_WAVE_P;
       const int32_t k = k0 + (lane & (MOOG_CT_GROUP - 1));
       f1[P] = f2[P] = 0;
       f3[P] = live[P] && (k0 < na[P] || k0 < nb[P]);
@@ -396,23 +371,23 @@ MOOG_ST_HD void moog_ct_narrow(const CtArgs& a, const CtObs& s, const double* f,
         f2[P] = !moog_ct_seg_outside_dop(v[2 * k], v[2 * k + 1], v[2 * k2], v[2 * k2 + 1], l.dop + 8 * ra[P]);
       }
     }
-    if (MOOG_CT_BALLOT(f3) == 0) break;
-    const uint64_t m1 = MOOG_CT_BALLOT(f1), m2 = MOOG_CT_BALLOT(f2);
-    MOOG_CT_EACH_LANE {
-      const int P = MOOG_CT_P;
+    if (MOOG_WAVE_BALLOT(f3) == 0) break;
+    const uint64_t m1 = MOOG_WAVE_BALLOT(f1), m2 = MOOG_WAVE_BALLOT(f2);
+    MOOG_WAVE_EACH_LANE {
+      const int P = MOOG_WAVE_P;
       const int g = lane / MOOG_CT_GROUP, t = lane & (MOOG_CT_GROUP - 1);
       const uint32_t g1 = moog_ct_gbits(m1, lane), g2 = moog_ct_gbits(m2, lane), below = (1u << t) - 1u;
       uint8_t* el = l.elist + g * 2 * MOOG_CT_MAXV;
-      if (f1[P]) el[ca[P] + moog_ct_popc(g1 & below)] = (uint8_t)(k0 + t);
-      if (f2[P]) el[MOOG_CT_MAXV + cb[P] + moog_ct_popc(g2 & below)] = (uint8_t)(k0 + t);
-      ca[P] += moog_ct_popc(g1); cb[P] += moog_ct_popc(g2);
+      if (f1[P]) el[ca[P] + MOOG_WAVE_POPC(g1 & below)] = (uint8_t)(k0 + t);
+      if (f2[P]) el[MOOG_CT_MAXV + cb[P] + MOOG_WAVE_POPC(g2 & below)] = (uint8_t)(k0 + t);
+      ca[P] += MOOG_WAVE_POPC(g1); cb[P] += MOOG_WAVE_POPC(g2);
     }
   }
-  MOOG_CT_SYNC();
+  MOOG_WAVE_SYNC();
   // the surviving edge pairs, 16 of a group at a time, until a hit
   for (int32_t base = 0;; base += MOOG_CT_GROUP) {
-    MOOG_CT_EACH_LANE {
-      const int P = MOOG_CT_P;
+    MOOG_WAVE_EACH_LANE {
+      const int P = MOOG_WAVE_P;
       const int g = lane / MOOG_CT_GROUP;
       const int32_t idx = base + (lane & (MOOG_CT_GROUP - 1)), total = ca[P] * cb[P];
       f1[P] = f2[P] = 0;
@@ -437,23 +412,23 @@ MOOG_ST_HD void moog_ct_narrow(const CtArgs& a, const CtObs& s, const double* f,
       f2[P] = kind == 2;
       if (kind == 4) par[P] = 1;
     }
-    if (MOOG_CT_BALLOT(f3) == 0) break;
-    const uint64_t m1 = MOOG_CT_BALLOT(f1), m2 = MOOG_CT_BALLOT(f2);
-    MOOG_CT_EACH_LANE {
-      const int P = MOOG_CT_P;
+    if (MOOG_WAVE_BALLOT(f3) == 0) break;
+    const uint64_t m1 = MOOG_WAVE_BALLOT(f1), m2 = MOOG_WAVE_BALLOT(f2);
+    MOOG_WAVE_EACH_LANE {
+      const int P = MOOG_WAVE_P;
       if (live[P] && moog_ct_gbits(m1, lane)) {
         res[P] = 1; proper[P] = moog_ct_gbits(m2, lane) != 0; live[P] = 0;
       }
     }
   }
   {
-    const uint64_t mp = MOOG_CT_BALLOT(par);
-    MOOG_CT_EACH_LANE par[MOOG_CT_P] = moog_ct_gbits(mp, lane) != 0;
+    const uint64_t mp = MOOG_WAVE_BALLOT(par);
+    MOOG_WAVE_EACH_LANE par[MOOG_WAVE_P] = moog_ct_gbits(mp, lane) != 0;
   }
   // path_in_path both ways: every vertex of one inside the other (possible only when its box does not leave the other's)
   for (int way = 0; way < 2; ++way) {
-    MOOG_CT_EACH_LANE {
-      const int P = MOOG_CT_P;
+    MOOG_WAVE_EACH_LANE {
+      const int P = MOOG_WAVE_P;
       const int32_t no = way ? nb[P] : na[P], ni = way ? na[P] : nb[P];   // outer and inner polygon
       const double* vo = way ? vb[P] : va[P];
       const double* vi = way ? va[P] : vb[P];
@@ -465,43 +440,43 @@ MOOG_ST_HD void moog_ct_narrow(const CtArgs& a, const CtObs& s, const double* f,
           f2[P] = !moog_ct_point_in_poly(vo, no, vi[2 * k], vi[2 * k + 1]);
       }
     }
-    const uint64_t m2 = MOOG_CT_BALLOT(f2);
-    MOOG_CT_EACH_LANE {
-      const int P = MOOG_CT_P;
+    const uint64_t m2 = MOOG_WAVE_BALLOT(f2);
+    MOOG_WAVE_EACH_LANE {
+      const int P = MOOG_WAVE_P;
       if (f1[P] && !moog_ct_gbits(m2, lane)) { res[P] = 1; proper[P] = 0; live[P] = 0; }
     }
   }
-  MOOG_CT_EACH_LANE {
-    const int P = MOOG_CT_P;
+  MOOG_WAVE_EACH_LANE {
+    const int P = MOOG_WAVE_P;
     if (live[P]) { res[P] = 0; proper[P] = !par[P]; }
   }
 }
 
 // The first nc candidates of the list, four at a time.
 MOOG_ST_HD void moog_ct_drain(const CtArgs& a, const CtObs& s, const double* f, const CtLds& l, int tid, int32_t nc) {
-  int32_t act[MOOG_CT_NP], ra[MOOG_CT_NP], rb[MOOG_CT_NP], res[MOOG_CT_NP], proper[MOOG_CT_NP];
-  int32_t act2[MOOG_CT_NP], res2[MOOG_CT_NP], proper2[MOOG_CT_NP];
+  int32_t act[MOOG_WAVE_NP], ra[MOOG_WAVE_NP], rb[MOOG_WAVE_NP], res[MOOG_WAVE_NP], proper[MOOG_WAVE_NP];
+  int32_t act2[MOOG_WAVE_NP], res2[MOOG_WAVE_NP], proper2[MOOG_WAVE_NP];
   for (int32_t c0 = 0; c0 < nc; c0 += MOOG_CT_GROUPS) {
-    MOOG_CT_EACH_LANE {
-      const int P = MOOG_CT_P;
+    MOOG_WAVE_EACH_LANE {
+      const int P = MOOG_WAVE_P;
       const int32_t c = c0 + lane / MOOG_CT_GROUP;
       act[P] = c < nc;
       const uint32_t pr = act[P] ? l.cand[c] : 0u;
       ra[P] = (int32_t)(pr >> 16); rb[P] = s.base1 + (int32_t)(pr & 0xffffu);
     }
     moog_ct_narrow(a, s, f, l, tid, act, ra, rb, res, proper);
-    MOOG_CT_EACH_LANE { const int P = MOOG_CT_P; act2[P] = act[P] && s.same && !proper[P]; res2[P] = res[P]; }
-    if (s.same && MOOG_CT_BALLOT(act2) != 0) {   // (j, i) on its own where (i, j) does not prove it
-      MOOG_CT_SYNC();
+    MOOG_WAVE_EACH_LANE { const int P = MOOG_WAVE_P; act2[P] = act[P] && s.same && !proper[P]; res2[P] = res[P]; }
+    if (s.same && MOOG_WAVE_BALLOT(act2) != 0) {   // (j, i) on its own where (i, j) does not prove it
+      MOOG_WAVE_SYNC();
       moog_ct_narrow(a, s, f, l, tid, act2, rb, ra, res2, proper2);
-      MOOG_CT_EACH_LANE { const int P = MOOG_CT_P; if (!act2[P]) res2[P] = res[P]; }
+      MOOG_WAVE_EACH_LANE { const int P = MOOG_WAVE_P; if (!act2[P]) res2[P] = res[P]; }
     }
-    MOOG_CT_EACH_LANE {
-      const int P = MOOG_CT_P;
+    MOOG_WAVE_EACH_LANE {
+      const int P = MOOG_WAVE_P;
       if ((lane & (MOOG_CT_GROUP - 1)) == 0) l.gres[lane / MOOG_CT_GROUP] = act[P] ? (res[P] | (res2[P] << 1)) : 0;
     }
-    MOOG_CT_SYNC();
-    MOOG_CT_EACH_LANE {
+    MOOG_WAVE_SYNC();
+    MOOG_WAVE_EACH_LANE {
       if (lane == 0)
         for (int g = 0; g < MOOG_CT_GROUPS && c0 + g < nc; ++g) {
           const uint32_t pr = l.cand[c0 + g], i = pr >> 16, j = pr & 0xffffu;
@@ -510,7 +485,7 @@ MOOG_ST_HD void moog_ct_drain(const CtArgs& a, const CtObs& s, const double* f, 
           if (s.same && (r & 2)) { const uint32_t k = j * (uint32_t)s.n1 + i; l.bits[k >> 5] |= 1u << (k & 31u); }
         }
     }
-    MOOG_CT_SYNC();
+    MOOG_WAVE_SYNC();
   }
 }
 
@@ -523,43 +498,43 @@ MOOG_ST_HD int32_t moog_ct_wave(const CtArgs& a, const CtObs& s, int64_t env, vo
   moog_ct_carve(s, lds_base, l);
   const int32_t NR = moog_ct_rows(s);
   const uint32_t NW = moog_ct_words(s);
-  MOOG_CT_EACH_LANE {
-    for (int32_t r = lane; r < NR; r += MOOG_CT_LANES) moog_ct_row(a, s, q, f, l, r);
-    for (uint32_t w = (uint32_t)lane; w < NW; w += MOOG_CT_LANES) l.bits[w] = 0u;
-    for (int32_t j = lane; j < s.n1; j += MOOG_CT_LANES) {
+  MOOG_WAVE_EACH_LANE {
+    for (int32_t r = lane; r < NR; r += MOOG_WAVE_LANES) moog_ct_row(a, s, q, f, l, r);
+    for (uint32_t w = (uint32_t)lane; w < NW; w += MOOG_WAVE_LANES) l.bits[w] = 0u;
+    for (int32_t j = lane; j < s.n1; j += MOOG_WAVE_LANES) {
       const int32_t id = s.rows[3 * (s.base1 + j)] >> 16;
       if (j == 0 || id != (s.rows[3 * (s.base1 + j - 1)] >> 16)) l.lstart[id] = j;
       if (j == s.n1 - 1) l.lstart[id + 1] = s.n1;
     }
   }
-  MOOG_CT_SYNC();
-  int32_t keep[MOOG_CT_NP];
-  uint32_t pair[MOOG_CT_NP];
+  MOOG_WAVE_SYNC();
+  int32_t keep[MOOG_WAVE_NP];
+  uint32_t pair[MOOG_WAVE_NP];
   // the active rows of each list, compacted in row order: the broad phase enumerates pairs of active rows only
   uint32_t A0 = 0, A1 = 0;
   const uint8_t* alist1 = s.same ? l.alist : l.alist + MOOG_MAX_SLOTS;
   for (int list = 0; list < (s.same ? 1 : 2); ++list) {
     const int32_t n = list ? s.n1 : s.n0, base = list ? s.base1 : 0;
     uint32_t cnt = 0;
-    for (int32_t r0 = 0; r0 < n; r0 += MOOG_CT_LANES) {
-      MOOG_CT_EACH_LANE keep[MOOG_CT_P] = r0 + lane < n && (l.meta[base + r0 + lane] & 1);
-      const uint64_t m = MOOG_CT_BALLOT(keep);
-      MOOG_CT_EACH_LANE
-        if (keep[MOOG_CT_P]) l.alist[list * MOOG_MAX_SLOTS + cnt + moog_ct_popc(m & ((1ull << lane) - 1ull))] = (uint8_t)(r0 + lane);
-      cnt += (uint32_t)moog_ct_popc(m);
+    for (int32_t r0 = 0; r0 < n; r0 += MOOG_WAVE_LANES) {
+      MOOG_WAVE_EACH_LANE keep[MOOG_WAVE_P] = r0 + lane < n && (l.meta[base + r0 + lane] & 1);
+      const uint64_t m = MOOG_WAVE_BALLOT(keep);
+      MOOG_WAVE_EACH_LANE
+        if (keep[MOOG_WAVE_P]) l.alist[list * MOOG_MAX_SLOTS + cnt + MOOG_WAVE_POPC(m & ((1ull << lane) - 1ull))] = (uint8_t)(r0 + lane);
+      cnt += (uint32_t)MOOG_WAVE_POPC(m);
     }
     if (list) A1 = cnt; else A0 = cnt;
   }
   if (s.same) A1 = A0;
-  MOOG_CT_SYNC();
+  MOOG_WAVE_SYNC();
   // broad phase: 64 pairs a pass -- with `same` the pairs i < j only; survivors are appended to the candidate list, which is
   // drained whenever it is full
   const uint32_t NP = (uint32_t)s.n0 * (uint32_t)s.n1;
   const uint32_t NB = s.same ? A0 * (A0 - (A0 ? 1u : 0u)) / 2u : A0 * A1;
   int32_t ncand = 0, seen = 0;
-  for (uint32_t p0 = 0; p0 < NB; p0 += MOOG_CT_LANES) {
-    MOOG_CT_EACH_LANE {
-      const int P = MOOG_CT_P;
+  for (uint32_t p0 = 0; p0 < NB; p0 += MOOG_WAVE_LANES) {
+    MOOG_WAVE_EACH_LANE {
+      const int P = MOOG_WAVE_P;
       const uint32_t p = p0 + (uint32_t)lane;
       keep[P] = 0; pair[P] = 0;
       if (p < NB) {
@@ -571,36 +546,36 @@ MOOG_ST_HD int32_t moog_ct_wave(const CtArgs& a, const CtObs& s, int64_t env, vo
         pair[P] = (i << 16) | j;
       }
     }
-    const uint64_t m = MOOG_CT_BALLOT(keep);
-    const int32_t total = moog_ct_popc(m);
+    const uint64_t m = MOOG_WAVE_BALLOT(keep);
+    const int32_t total = MOOG_WAVE_POPC(m);
     seen += total;
     for (int32_t done = 0; done < total;) {
       const int32_t room = a.chunk - ncand, take = total - done < room ? total - done : room;
-      MOOG_CT_EACH_LANE {
-        const int P = MOOG_CT_P;
-        const int32_t rank = moog_ct_popc(m & ((1ull << lane) - 1ull));
+      MOOG_WAVE_EACH_LANE {
+        const int P = MOOG_WAVE_P;
+        const int32_t rank = MOOG_WAVE_POPC(m & ((1ull << lane) - 1ull));
         if (keep[P] && rank >= done && rank < done + take) l.cand[ncand + rank - done] = pair[P];
       }
       ncand += take; done += take;
       if (ncand == a.chunk) {
-        MOOG_CT_SYNC();
+        MOOG_WAVE_SYNC();
         moog_ct_drain(a, s, f, l, tid, ncand);
         ncand = 0;
       }
     }
   }
-  MOOG_CT_SYNC();
+  MOOG_WAVE_SYNC();
   if (ncand) moog_ct_drain(a, s, f, l, tid, ncand);
-  MOOG_CT_SYNC();
+  MOOG_WAVE_SYNC();
   // the env's block of bytes: byte stores up to the first dword boundary and behind the last, dword stores in between
   const uint32_t NE = s.mode == MOOG_CONTACTS_PAIR ? NP : (uint32_t)s.n0 * (uint32_t)s.n_layers1;
   uint8_t* out = s.out + env * (int64_t)NE;
   uint32_t head = (uint32_t)((4u - ((uintptr_t)out & 3u)) & 3u);
   if (head > NE) head = NE;
   const uint32_t nd = (NE - head) >> 2, tail0 = head + 4u * nd;
-  MOOG_CT_EACH_LANE {
+  MOOG_WAVE_EACH_LANE {
     if ((uint32_t)lane < head) out[lane] = (uint8_t)moog_ct_element(s, l, (uint32_t)lane);
-    for (uint32_t d = (uint32_t)lane; d < nd; d += MOOG_CT_LANES) {
+    for (uint32_t d = (uint32_t)lane; d < nd; d += MOOG_WAVE_LANES) {
       const uint32_t k = head + 4u * d;
       *(uint32_t*)(out + k) = moog_ct_four(s, l, k);
     }

@@ -5,7 +5,7 @@
 #include "moog_contacts.h"
 
 // Grid: x = env, y = observer; a workgroup is one wavefront.  The dynamic LDS block is sized for the launch's largest observer.
-__global__ __launch_bounds__(MOOG_CT_LANES) void moog_contacts_kernel(CtArgs a) {
+__global__ __launch_bounds__(MOOG_WAVE_LANES) void moog_contacts_kernel(CtArgs a) {
   extern __shared__ double moog_ct_lds[];
   moog_ct_wave(a, a.c[blockIdx.y], (int64_t)blockIdx.x, moog_ct_lds, (int)threadIdx.x);
 }
@@ -18,5 +18,5 @@ void moog_contacts_launch(CtArgs a, hipStream_t stream) {
     const size_t b = moog_ct_lds_bytes(a.c[k]);
     if (b > lds) lds = b;
   }
-  hipLaunchKernelGGL(moog_contacts_kernel, dim3((uint32_t)a.n_envs, (uint32_t)a.n_obs), dim3(MOOG_CT_LANES), lds, stream, a);
+  hipLaunchKernelGGL(moog_contacts_kernel, dim3((uint32_t)a.n_envs, (uint32_t)a.n_obs), dim3(MOOG_WAVE_LANES), lds, stream, a);
 }

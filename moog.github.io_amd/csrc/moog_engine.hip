@@ -77,12 +77,27 @@ struct RView {
   uint8_t* s_bg = nullptr;
 };
 
-// A sprite table of the engine (moog_engine_add_table): the kernel's descriptor, its rows on the device, and -- in desc.out --
-// the bound buffer (moog_engine_set_table_buffer), or null.  `traj`: what the step kernel's recorder needs of the table (its
-// rows, its column ids) and -- in traj.out -- the trajectory bound for the sequences to come (moog_engine_set_table_trajectory).
-struct STable {
-  StTable desc{};
-  int32_t* d_rows = nullptr;
+// An observer of the engine that a launch of its own refreshes (launch_tables): a sprite table (moog_engine_add_table), a ray
+// sensor (moog_engine_add_sensor) or a contacts observer (moog_engine_add_contacts).  Each is the kernel's descriptor, the device
+// arrays the descriptor points into (its rows; a sensor's directions too), and -- in desc.out -- the bound buffer
+// (moog_engine_set_*_buffer), or null.
+template <class Desc>
+struct Attached {
+  Desc desc{};
+  void* d_mem[2] = {nullptr, nullptr};
+};
+// The observers of one kind: the first n slots are in use (an add call hands out the next), n_bound of them have a buffer.
+template <class SlotT, int MAX_>
+struct ObserverSet {
+  typedef SlotT Slot;
+  static constexpr int MAX = MAX_;
+  Slot at[MAX_];
+  int n = 0, n_bound = 0;
+};
+
+// A sprite table has more.  `traj`: what the step kernel's recorder needs of the table (its rows, its column ids) and -- in
+// traj.out -- the trajectory bound for the sequences to come (moog_engine_set_table_trajectory).
+struct STable : Attached<StTable> {
   TrajTable traj{};
 };
 
@@ -93,21 +108,6 @@ struct SegView {
   uint32_t* d_ids = nullptr;   // [n_envs][slots] the emitter's rgb_override: slot_id in the low byte (replicated per env: the emitter indexes it by env)
   uint8_t* ids = nullptr;      // [n_envs][height][width] (moog_engine_set_segmentation_image)
   uint8_t* pad_ids = nullptr;  // [n_envs][height][pad_w] when the width is no multiple of 16 (cropped into `ids`)
-};
-
-// A ray sensor of the engine (moog_engine_add_sensor): the kernel's descriptor, its rows and directions on the device, and -- in
-// desc.out -- the bound buffer (moog_engine_set_sensor_buffer), or null.
-struct SSensor {
-  RsSensor desc{};
-  int32_t* d_rows = nullptr;
-  double* d_dirs = nullptr;
-};
-
-// A contacts observer of the engine (moog_engine_add_contacts): the kernel's descriptor, its rows on the device, and -- in
-// desc.out -- the bound buffer (moog_engine_set_contacts_buffer), or null.
-struct SContacts {
-  CtObs desc{};
-  int32_t* d_rows = nullptr;
 };
 
 struct moog_engine {
@@ -137,12 +137,9 @@ struct moog_engine {
   uint8_t* late_mask = nullptr;   // [n_envs]
   RView views[MOOG_MAX_VIEWS];
   int n_views = 1;               // views[0] and the extra views added so far
-  STable tables[MOOG_MAX_TABLES];
-  int n_tables = 0, n_bound_tables = 0;   // tables added so far; how many of them have a buffer
-  SSensor sensors[MOOG_MAX_SENSORS];
-  int n_sensors = 0, n_bound_sensors = 0;   // the same for ray sensors
-  SContacts contacts[MOOG_MAX_CONTACTS];
-  int n_contacts = 0, n_bound_contacts = 0;   // and for contacts observers
+  ObserverSet<STable, MOOG_MAX_TABLES> tables;
+  ObserverSet<Attached<RsSensor>, MOOG_MAX_SENSORS> sensors;
+  ObserverSet<Attached<CtObs>, MOOG_MAX_CONTACTS> contacts;
   SegView segs[MOOG_MAX_SEGMENTATIONS];
   int n_segs = 0, n_bound_segs = 0;       // segmentations added so far; how many of them have an image
   bool frameless = false;        // render 0 x 0: the program draws no frames (no raster state at all)
@@ -192,6 +189,75 @@ struct moog_engine {
   int32_t* pe_min = nullptr;        // pinned host word: first slot of the prefix seen changing in the middle of an episode
 };
 
+// ---- what the sprite tables, ray sensors and contacts observers share ----------------------------------------------------------
+// The three kinds differ in their describe function (moog_st_describe, moog_rs_describe, moog_ct_describe: descriptor layouts
+// and id conventions of their own), in the arrays they upload and in the alignment their kernel's stores need; the rest of an
+// add call, a set-buffer call, a launch's gathering and the destroy is here, over ObserverSet.
+
+// An add call's checks; `slot`: where the new observer goes.  It counts only once the call has succeeded (`set.n++`), so a
+// call that fails leaves the slot as it found it.
+template <class Set>
+static int next_observer(moog_engine* e, Set moog_engine::*which, const void* desc, const int32_t* index, const char* full,
+                         typename Set::Slot** slot) {
+  if (!e || !desc || !index) return fail(MOOG_E_INVALID, "null argument");
+  Set& set = e->*which;
+  if (set.n >= Set::MAX) return fail(MOOG_E_INVALID, full);
+  *slot = &set.at[set.n];
+  return MOOG_OK;
+}
+
+// Device copies of an observer's arrays (at most two, d_mem of its slot).  A failure frees everything this call allocated.
+struct Upload {
+  const void* host;
+  size_t bytes;
+};
+static int upload_observer(moog_engine* e, const Upload* up, int n_up, void** d_mem) {
+  HIPCHK(hipSetDevice(e->device));
+  hipError_t err = hipSuccess;
+  for (int k = 0; k < n_up && err == hipSuccess; ++k) {
+    err = hipMalloc(&d_mem[k], up[k].bytes);
+    if (err == hipSuccess) err = hipMemcpy(d_mem[k], up[k].host, up[k].bytes, hipMemcpyHostToDevice);
+  }
+  if (err == hipSuccess) return MOOG_OK;
+  for (int k = 0; k < n_up; ++k) {
+    if (d_mem[k]) hipFree(d_mem[k]);
+    d_mem[k] = nullptr;
+  }
+  (void)hipGetLastError();
+  return fail(MOOG_E_HIP, std::string("hipMalloc / hipMemcpy of an observer's arrays: ") + hipGetErrorString(err));
+}
+
+// A set-buffer call: binds `dev` (null: unbinds) and keeps the bound count.  align_mask: the address bits that must be 0,
+// given the descriptor.
+template <class Set>
+static int bind_observer(moog_engine* e, Set moog_engine::*which, int32_t index, void* dev, const char* none,
+                         uintptr_t (*align_mask)(const decltype(Set::Slot::desc)&), const char* misaligned) {
+  if (!e) return fail(MOOG_E_INVALID, "null engine");
+  Set& set = e->*which;
+  if (index < 0 || index >= set.n) return fail(MOOG_E_INVALID, none);
+  auto& d = set.at[index].desc;
+  if ((uintptr_t)dev & align_mask(d)) return fail(MOOG_E_INVALID, misaligned);
+  set.n_bound += (dev ? 1 : 0) - (d.out ? 1 : 0);
+  d.out = (decltype(d.out))dev;
+  return MOOG_OK;
+}
+
+// The descriptors of a set's bound observers, in index order, into a launch's argument array; how many.
+template <class Set, class Desc>
+static int gather_bound(const Set& set, Desc* out) {
+  int n = 0;
+  for (int k = 0; k < set.n; ++k)
+    if (set.at[k].desc.out) out[n++] = set.at[k].desc;
+  return n;
+}
+
+template <class Set>
+static void free_observers(Set& set) {
+  for (typename Set::Slot& t : set.at)
+    for (void* p : t.d_mem)
+      if (p) hipFree(p);
+}
+
 static void free_engine(moog_engine* e) {
   if (e->d_prog) hipFree(e->d_prog);
   if (e->d_vslot) hipFree(e->d_vslot);
@@ -204,12 +270,9 @@ static void free_engine(moog_engine* e) {
     if (v.aa_tables) hipFree(v.aa_tables);
     if (v.rows_seen) hipHostFree(v.rows_seen);
   }
-  for (STable& t : e->tables) if (t.d_rows) hipFree(t.d_rows);
-  for (SSensor& t : e->sensors) {
-    if (t.d_rows) hipFree(t.d_rows);
-    if (t.d_dirs) hipFree(t.d_dirs);
-  }
-  for (SContacts& t : e->contacts) if (t.d_rows) hipFree(t.d_rows);
+  free_observers(e->tables);
+  free_observers(e->sensors);
+  free_observers(e->contacts);
   for (SegView& g : e->segs) {
     if (g.v.draw) hipFree(g.v.draw);
     if (g.v.rows_seen) hipHostFree(g.v.rows_seen);
@@ -1212,9 +1275,9 @@ static int launch_frames(moog_engine* e, uint8_t* image, hipStream_t s, bool dra
 // (moog_contacts.h), inside one MOOG_K_TABLES bracket.  An engine without any returns at the first comparison.
 enum { OBSERVE_TABLES = 1, OBSERVE_SENSORS = 2, OBSERVE_CONTACTS = 4 };
 static int launch_tables(moog_engine* e, hipStream_t s, int what = OBSERVE_TABLES | OBSERVE_SENSORS | OBSERVE_CONTACTS) {
-  if (e->n_bound_tables + e->n_bound_sensors + e->n_bound_contacts == 0) return MOOG_OK;
-  const bool tables = (what & OBSERVE_TABLES) && e->n_bound_tables, sensors = (what & OBSERVE_SENSORS) && e->n_bound_sensors;
-  const bool contacts = (what & OBSERVE_CONTACTS) && e->n_bound_contacts;
+  if (e->tables.n_bound + e->sensors.n_bound + e->contacts.n_bound == 0) return MOOG_OK;
+  const bool tables = (what & OBSERVE_TABLES) && e->tables.n_bound, sensors = (what & OBSERVE_SENSORS) && e->sensors.n_bound;
+  const bool contacts = (what & OBSERVE_CONTACTS) && e->contacts.n_bound;
   if (!tables && !sensors && !contacts) return MOOG_OK;
   {
     Bracket br(e, MOOG_K_TABLES, s);
@@ -1222,24 +1285,21 @@ static int launch_tables(moog_engine* e, hipStream_t s, int what = OBSERVE_TABLE
       StArgs a;
       a.f64 = e->view.f64; a.i32 = e->view.i32;
       a.f64_per_env = e->L.f64_per_env; a.i32_per_env = e->L.i32_per_env;
-      a.n_envs = e->n_envs; a.chunk_envs = 0; a.o_flags = e->L.o_flags; a.n_tables = 0;
-      for (int k = 0; k < e->n_tables; ++k)
-        if (e->tables[k].desc.out) a.t[a.n_tables++] = e->tables[k].desc;
+      a.n_envs = e->n_envs; a.chunk_envs = 0; a.o_flags = e->L.o_flags;
+      a.n_tables = gather_bound(e->tables, a.t);
       for (int k = a.n_tables; k < MOOG_MAX_TABLES; ++k) memset(&a.t[k], 0, sizeof a.t[k]);
       moog_sprite_table_launch(a, s);
     }
     if (sensors) {
       RsArgs a;
       moog_rs_args(&e->L, e->view.f64, e->view.i32, e->n_envs, &a);
-      for (int k = 0; k < e->n_sensors; ++k)
-        if (e->sensors[k].desc.out) a.s[a.n_sensors++] = e->sensors[k].desc;
+      a.n_sensors = gather_bound(e->sensors, a.s);
       moog_ray_sensor_launch(a, s);
     }
     if (contacts) {
       CtArgs a;
       moog_ct_args(&e->L, e->view.f64, e->view.i32, e->n_envs, &a);
-      for (int k = 0; k < e->n_contacts; ++k)
-        if (e->contacts[k].desc.out) a.c[a.n_obs++] = e->contacts[k].desc;
+      a.n_obs = gather_bound(e->contacts, a.c);
       moog_contacts_launch(a, s);
     }
   }
@@ -1328,8 +1388,8 @@ static int step_call(moog_engine* e, const void* actions_dev, int32_t n_steps, i
     a.reward_seq = rewards_dev;
     a.reward_seq_stride = reward_step_elems;
     int n_traj = 0;   // (the tables with a trajectory first: the kernels stop at the first descriptor without a buffer)
-    for (int k = 0; k < e->n_tables; ++k)
-      if (e->tables[k].traj.out) a.traj[n_traj++] = e->tables[k].traj;
+    for (int k = 0; k < e->tables.n; ++k)
+      if (e->tables.at[k].traj.out) a.traj[n_traj++] = e->tables.at[k].traj;
   }
   int rc;
   const bool emit = out && out->image && step_emits_draw(e);
@@ -1672,45 +1732,41 @@ int moog_engine_set_segmentation_image(moog_engine_t* e, int32_t index, uint8_t*
   return MOOG_OK;
 }
 
+// ---- sprite tables, ray sensors, contacts observers: add / set buffer / observe (the helpers are above free_engine) ------------
 int moog_engine_add_table(moog_engine_t* e, const moog_table_t* table_desc, int32_t* table) {
-  if (!e || !table_desc || !table) return fail(MOOG_E_INVALID, "null argument");
-  if (e->n_tables >= MOOG_MAX_TABLES) return fail(MOOG_E_INVALID, "at most MOOG_MAX_TABLES sprite tables per engine");
-  STable& t = e->tables[e->n_tables];
+  STable* t;
+  int rc = next_observer(e, &moog_engine::tables, table_desc, table, "at most MOOG_MAX_TABLES sprite tables per engine", &t);
+  if (rc) return rc;
   int32_t rows[MOOG_MAX_SLOTS];
   StTable d;
   memset(&d, 0, sizeof d);
   const char* why = moog_st_describe(&e->prog, &e->L, table_desc, &d, rows);
   if (why) return fail(MOOG_E_INVALID, why);
-  HIPCHK(hipSetDevice(e->device));
-  HIPCHK(hipMalloc(&t.d_rows, sizeof(int32_t) * (size_t)table_desc->n_rows));
-  HIPCHK(hipMemcpy(t.d_rows, rows, sizeof(int32_t) * (size_t)table_desc->n_rows, hipMemcpyHostToDevice));
-  d.rows = t.d_rows;
-  t.desc = d;
-  memset(&t.traj, 0, sizeof t.traj);
-  t.traj.rows = t.d_rows;
-  t.traj.n_rows = table_desc->n_rows;
-  t.traj.n_cols = (uint8_t)table_desc->n_cols;
-  t.traj.dtype = (uint8_t)table_desc->dtype;
-  for (int c = 0; c < table_desc->n_cols; ++c) t.traj.cols[c / 8] |= (uint64_t)(uint8_t)table_desc->cols[c] << (8 * (c % 8));
-  *table = e->n_tables++;
+  const Upload up[] = {{rows, sizeof(int32_t) * (size_t)table_desc->n_rows}};
+  rc = upload_observer(e, up, 1, t->d_mem);
+  if (rc) return rc;
+  d.rows = (const int32_t*)t->d_mem[0];
+  t->desc = d;
+  memset(&t->traj, 0, sizeof t->traj);
+  t->traj.rows = d.rows;
+  t->traj.n_rows = table_desc->n_rows;
+  t->traj.n_cols = (uint8_t)table_desc->n_cols;
+  t->traj.dtype = (uint8_t)table_desc->dtype;
+  for (int c = 0; c < table_desc->n_cols; ++c) t->traj.cols[c / 8] |= (uint64_t)(uint8_t)table_desc->cols[c] << (8 * (c % 8));
+  *table = e->tables.n++;
   return MOOG_OK;
 }
 
 int moog_engine_set_table_buffer(moog_engine_t* e, int32_t table, void* table_dev) {
-  if (!e) return fail(MOOG_E_INVALID, "null engine");
-  if (table < 0 || table >= e->n_tables) return fail(MOOG_E_INVALID, "no such sprite table");
-  StTable& d = e->tables[table].desc;
-  if ((uintptr_t)table_dev & (d.dtype == MOOG_TABLE_F16 ? 1u : 3u))
-    return fail(MOOG_E_INVALID, "sprite table buffer must be aligned to its element type");
-  e->n_bound_tables += (table_dev ? 1 : 0) - (d.out ? 1 : 0);
-  d.out = table_dev;
-  return MOOG_OK;
+  return bind_observer(e, &moog_engine::tables, table, table_dev, "no such sprite table",
+                       [](const StTable& d) -> uintptr_t { return d.dtype == MOOG_TABLE_F16 ? 1u : 3u; },
+                       "sprite table buffer must be aligned to its element type");
 }
 
 int moog_engine_set_table_trajectory(moog_engine_t* e, int32_t table, void* traj_dev, int64_t step_elems) {
   if (!e) return fail(MOOG_E_INVALID, "null engine");
-  if (table < 0 || table >= e->n_tables) return fail(MOOG_E_INVALID, "no such sprite table");
-  TrajTable& t = e->tables[table].traj;
+  if (table < 0 || table >= e->tables.n) return fail(MOOG_E_INVALID, "no such sprite table");
+  TrajTable& t = e->tables.at[table].traj;
   if ((uintptr_t)traj_dev & (t.dtype == MOOG_TABLE_F16 ? 1u : 3u))
     return fail(MOOG_E_INVALID, "sprite table trajectory must be aligned to its element type");
   if (traj_dev && step_elems < (int64_t)e->n_envs * t.n_rows * (int64_t)t.n_cols)
@@ -1727,35 +1783,29 @@ int moog_engine_observe_tables(moog_engine_t* e, void* hip_stream) {
 }
 
 int moog_engine_add_sensor(moog_engine_t* e, const moog_sensor_t* sensor_desc, int32_t* sensor) {
-  if (!e || !sensor_desc || !sensor) return fail(MOOG_E_INVALID, "null argument");
-  if (e->n_sensors >= MOOG_MAX_SENSORS) return fail(MOOG_E_INVALID, "at most MOOG_MAX_SENSORS ray sensors per engine");
-  SSensor& t = e->sensors[e->n_sensors];
+  Attached<RsSensor>* t;
+  int rc = next_observer(e, &moog_engine::sensors, sensor_desc, sensor, "at most MOOG_MAX_SENSORS ray sensors per engine", &t);
+  if (rc) return rc;
   int32_t rows[3 * MOOG_MAX_SLOTS];
   RsSensor d;
   memset(&d, 0, sizeof d);
   const char* why = moog_rs_describe(&e->prog, &e->L, sensor_desc, &d, rows);
   if (why) return fail(MOOG_E_INVALID, why);
-  const size_t rows_bytes = sizeof(int32_t) * 3 * (size_t)sensor_desc->n_rows, dirs_bytes = sizeof(double) * 2 * (size_t)sensor_desc->n_rays;
-  HIPCHK(hipSetDevice(e->device));
-  HIPCHK(hipMalloc(&t.d_rows, rows_bytes));
-  HIPCHK(hipMemcpy(t.d_rows, rows, rows_bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&t.d_dirs, dirs_bytes));
-  HIPCHK(hipMemcpy(t.d_dirs, sensor_desc->dirs, dirs_bytes, hipMemcpyHostToDevice));
-  d.rows = t.d_rows;
-  d.dirs = t.d_dirs;
-  t.desc = d;
-  *sensor = e->n_sensors++;
+  const Upload up[] = {{rows, sizeof(int32_t) * 3 * (size_t)sensor_desc->n_rows},
+                       {sensor_desc->dirs, sizeof(double) * 2 * (size_t)sensor_desc->n_rays}};
+  rc = upload_observer(e, up, 2, t->d_mem);
+  if (rc) return rc;
+  d.rows = (const int32_t*)t->d_mem[0];
+  d.dirs = (const double*)t->d_mem[1];
+  t->desc = d;
+  *sensor = e->sensors.n++;
   return MOOG_OK;
 }
 
 int moog_engine_set_sensor_buffer(moog_engine_t* e, int32_t sensor, void* sensor_dev) {
-  if (!e) return fail(MOOG_E_INVALID, "null engine");
-  if (sensor < 0 || sensor >= e->n_sensors) return fail(MOOG_E_INVALID, "no such ray sensor");
-  RsSensor& d = e->sensors[sensor].desc;
-  if ((uintptr_t)sensor_dev & 3u) return fail(MOOG_E_INVALID, "ray sensor buffer must be 4-byte aligned (a float16 ray is one dword)");
-  e->n_bound_sensors += (sensor_dev ? 1 : 0) - (d.out ? 1 : 0);
-  d.out = sensor_dev;
-  return MOOG_OK;
+  return bind_observer(e, &moog_engine::sensors, sensor, sensor_dev, "no such ray sensor",
+                       [](const RsSensor&) -> uintptr_t { return 3u; },
+                       "ray sensor buffer must be 4-byte aligned (a float16 ray is one dword)");
 }
 
 int moog_engine_observe_sensors(moog_engine_t* e, void* hip_stream) {
@@ -1765,31 +1815,28 @@ int moog_engine_observe_sensors(moog_engine_t* e, void* hip_stream) {
 }
 
 int moog_engine_add_contacts(moog_engine_t* e, const moog_contacts_t* contacts_desc, int32_t* contacts) {
-  if (!e || !contacts_desc || !contacts) return fail(MOOG_E_INVALID, "null argument");
-  if (e->n_contacts >= MOOG_MAX_CONTACTS) return fail(MOOG_E_INVALID, "at most MOOG_MAX_CONTACTS contacts observers per engine");
-  SContacts& t = e->contacts[e->n_contacts];
+  Attached<CtObs>* t;
+  int rc = next_observer(e, &moog_engine::contacts, contacts_desc, contacts,
+                         "at most MOOG_MAX_CONTACTS contacts observers per engine", &t);
+  if (rc) return rc;
   int32_t rows[3 * 2 * MOOG_MAX_SLOTS];
   CtObs d;
   memset(&d, 0, sizeof d);
   const char* why = moog_ct_describe(&e->prog, &e->L, contacts_desc, &d, rows);
   if (why) return fail(MOOG_E_INVALID, why);
-  const size_t rows_bytes = sizeof(int32_t) * 3 * ((size_t)contacts_desc->n_rows_0 + (size_t)contacts_desc->n_rows_1);
-  HIPCHK(hipSetDevice(e->device));
-  HIPCHK(hipMalloc(&t.d_rows, rows_bytes));
-  HIPCHK(hipMemcpy(t.d_rows, rows, rows_bytes, hipMemcpyHostToDevice));
-  d.rows = t.d_rows;
-  t.desc = d;
-  *contacts = e->n_contacts++;
+  const Upload up[] = {{rows, sizeof(int32_t) * 3 * ((size_t)contacts_desc->n_rows_0 + (size_t)contacts_desc->n_rows_1)}};
+  rc = upload_observer(e, up, 1, t->d_mem);
+  if (rc) return rc;
+  d.rows = (const int32_t*)t->d_mem[0];
+  t->desc = d;
+  *contacts = e->contacts.n++;
   return MOOG_OK;
 }
 
 int moog_engine_set_contacts_buffer(moog_engine_t* e, int32_t contacts, void* contacts_dev) {
-  if (!e) return fail(MOOG_E_INVALID, "null engine");
-  if (contacts < 0 || contacts >= e->n_contacts) return fail(MOOG_E_INVALID, "no such contacts observer");
-  CtObs& d = e->contacts[contacts].desc;
-  e->n_bound_contacts += (contacts_dev ? 1 : 0) - (d.out ? 1 : 0);
-  d.out = (uint8_t*)contacts_dev;
-  return MOOG_OK;
+  // (no alignment asked: the kernel stores bytes up to the first dword boundary of an env's block)
+  return bind_observer(e, &moog_engine::contacts, contacts, contacts_dev, "no such contacts observer",
+                       [](const CtObs&) -> uintptr_t { return 0u; }, "");
 }
 
 int moog_engine_observe_contacts(moog_engine_t* e, void* hip_stream) {

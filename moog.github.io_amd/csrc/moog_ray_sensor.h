@@ -46,10 +46,8 @@
 // No cull: a per-sprite bound against the ray would have to be proven never to change a result (inclusive ends, NaN
 // vertices, t <= max_range at the rounding of one division); it is left out rather than argued.
 //
-// The host model needs the cross-lane steps too, so the wave function is written once over a few macros: on the device a
-// "for every lane" block runs for the lane the thread is, per-lane variables are scalars, a shuffle is a shuffle; on the host
-// the block loops over 64 lanes, per-lane variables are arrays, and a shuffle reads the other lane's element (every shuffle
-// sits in a block of its own that only reads, so the host loop sees the values from before the step, as the wave does).
+// The host model needs the cross-lane steps too, so the wave function is written once over the lane model of
+// moog_wave_model.h.
 #ifndef MOOG_RAY_SENSOR_H_
 #define MOOG_RAY_SENSOR_H_
 
@@ -59,10 +57,10 @@
 #include <string.h>
 
 #include "moog_sprite_table.h"
+#include "moog_wave_model.h"
 
-#define MOOG_RS_LANES 64
 #define MOOG_RS_CHUNK 128                                     // edges staged at a time
-#define MOOG_RS_ROWS_PER_LANE (MOOG_MAX_SLOTS / MOOG_RS_LANES)
+#define MOOG_RS_ROWS_PER_LANE (MOOG_MAX_SLOTS / MOOG_WAVE_LANES)
 #define MOOG_RS_NO_KEY 0x7fffffff
 
 // ---- descriptors -------------------------------------------------------------------------------------------------------
@@ -204,21 +202,6 @@ MOOG_ST_HD uint32_t moog_rs_cast(double v, int32_t dtype) {
 #ifndef MOOG_RS_COSSIN
 #define MOOG_RS_COSSIN(ang, c, s) ((c) = cos(ang), (s) = sin(ang))
 #endif
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MOOG_RS_NP 1
-#define MOOG_RS_EACH_LANE for (int lane = tid, once_ = 1; once_; once_ = 0)
-#define MOOG_RS_P 0
-#define MOOG_RS_SYNC() __syncthreads()
-#define MOOG_RS_SHFL_XOR(arr, m) __shfl_xor((arr)[0], (m))
-#define MOOG_RS_SHFL_UP(arr, d) __shfl_up((arr)[0], (d))
-#else
-#define MOOG_RS_NP MOOG_RS_LANES
-#define MOOG_RS_EACH_LANE for (int lane = 0; lane < MOOG_RS_LANES; ++lane)
-#define MOOG_RS_P lane
-#define MOOG_RS_SYNC() (void)tid
-#define MOOG_RS_SHFL_XOR(arr, m) (arr)[lane ^ (m)]
-#define MOOG_RS_SHFL_UP(arr, d) (arr)[lane >= (d) ? lane - (d) : lane]
-#endif
 
 // Sensor s of env `env`, by one wave: tid is the thread's lane on the device and unused on the host, where one call runs
 // all 64 lanes.
@@ -229,7 +212,7 @@ MOOG_ST_HD void moog_rs_wave(const RsArgs& a, const RsSensor& s, int64_t env, Rs
   const double ox = f[a.o_pos + 2 * s.origin_slot], oy = f[a.o_pos + 2 * s.origin_slot + 1];
   const bool follow = (s.flags & MOOG_SENSOR_FOLLOW_ANGLE) != 0;
   if (follow) {
-    MOOG_RS_EACH_LANE {
+    MOOG_WAVE_EACH_LANE {
       if (lane == 0) {
         const double ang = f[a.o_angle + s.origin_slot];
         MOOG_RS_COSSIN(ang, lds.cs[0], lds.cs[1]);
@@ -237,37 +220,37 @@ MOOG_ST_HD void moog_rs_wave(const RsArgs& a, const RsSensor& s, int64_t env, Rs
     }
   }
   // the rows' edge counts, prefix-summed: four rows a lane, then a scan of the lanes' sums
-  int32_t tot[MOOG_RS_NP], inc[MOOG_RS_NP], up[MOOG_RS_NP];
-  MOOG_RS_EACH_LANE {
+  int32_t tot[MOOG_WAVE_NP], inc[MOOG_WAVE_NP], up[MOOG_WAVE_NP];
+  MOOG_WAVE_EACH_LANE {
     int32_t sum = 0;
     for (int j = 0; j < MOOG_RS_ROWS_PER_LANE; ++j) {
       const int32_t r = MOOG_RS_ROWS_PER_LANE * lane + j;
       lds.estart[r] = sum;
       if (alive && r < s.n_rows) sum += moog_rs_row_edges(a, s, q, r);
     }
-    tot[MOOG_RS_P] = inc[MOOG_RS_P] = sum;
+    tot[MOOG_WAVE_P] = inc[MOOG_WAVE_P] = sum;
   }
-  for (int d = 1; d < MOOG_RS_LANES; d <<= 1) {
-    MOOG_RS_EACH_LANE up[MOOG_RS_P] = MOOG_RS_SHFL_UP(inc, d);
-    MOOG_RS_EACH_LANE if (lane >= d) inc[MOOG_RS_P] += up[MOOG_RS_P];
+  for (int d = 1; d < MOOG_WAVE_LANES; d <<= 1) {
+    MOOG_WAVE_EACH_LANE up[MOOG_WAVE_P] = MOOG_WAVE_SHFL_UP(inc, d);
+    MOOG_WAVE_EACH_LANE if (lane >= d) inc[MOOG_WAVE_P] += up[MOOG_WAVE_P];
   }
-  MOOG_RS_EACH_LANE {
-    const int32_t base = inc[MOOG_RS_P] - tot[MOOG_RS_P];
+  MOOG_WAVE_EACH_LANE {
+    const int32_t base = inc[MOOG_WAVE_P] - tot[MOOG_WAVE_P];
     for (int j = 0; j < MOOG_RS_ROWS_PER_LANE; ++j) lds.estart[MOOG_RS_ROWS_PER_LANE * lane + j] += base;
-    if (lane == MOOG_RS_LANES - 1) lds.estart[MOOG_MAX_SLOTS] = inc[MOOG_RS_P];
+    if (lane == MOOG_WAVE_LANES - 1) lds.estart[MOOG_MAX_SLOTS] = inc[MOOG_WAVE_P];
   }
-  MOOG_RS_SYNC();
+  MOOG_WAVE_SYNC();
   const int32_t N = lds.estart[MOOG_MAX_SLOTS];
   const double c = follow ? lds.cs[0] : 1.0, sn = follow ? lds.cs[1] : 0.0;
 
   const int32_t R = s.n_rays;
   int32_t G = 1;
-  while (2 * G * R <= MOOG_RS_LANES) G *= 2;
-  const int32_t per_pass = MOOG_RS_LANES / G;
+  while (2 * G * R <= MOOG_WAVE_LANES) G *= 2;
+  const int32_t per_pass = MOOG_WAVE_LANES / G;
   for (int32_t ray0 = 0; ray0 < R; ray0 += per_pass) {
-    double dx[MOOG_RS_NP], dy[MOOG_RS_NP], bt[MOOG_RS_NP], ot[MOOG_RS_NP];
-    int32_t bk[MOOG_RS_NP], ok[MOOG_RS_NP];
-    MOOG_RS_EACH_LANE {
+    double dx[MOOG_WAVE_NP], dy[MOOG_WAVE_NP], bt[MOOG_WAVE_NP], ot[MOOG_WAVE_NP];
+    int32_t bk[MOOG_WAVE_NP], ok[MOOG_WAVE_NP];
+    MOOG_WAVE_EACH_LANE {
       const int32_t ray = ray0 + lane / G;
       double x = 0.0, y = 0.0;
       if (ray < R) { x = s.dirs[2 * ray]; y = s.dirs[2 * ray + 1]; }
@@ -275,45 +258,45 @@ MOOG_ST_HD void moog_rs_wave(const RsArgs& a, const RsSensor& s, int64_t env, Rs
         const double rx = c * x - sn * y, ry = sn * x + c * y;
         x = rx; y = ry;
       }
-      dx[MOOG_RS_P] = x; dy[MOOG_RS_P] = y;
-      bt[MOOG_RS_P] = (double)INFINITY; bk[MOOG_RS_P] = MOOG_RS_NO_KEY;
+      dx[MOOG_WAVE_P] = x; dy[MOOG_WAVE_P] = y;
+      bt[MOOG_WAVE_P] = (double)INFINITY; bk[MOOG_WAVE_P] = MOOG_RS_NO_KEY;
     }
     for (int32_t e0 = 0; e0 < N; e0 += a.chunk) {
       const int32_t nc = N - e0 < a.chunk ? N - e0 : a.chunk;
       if (ray0 == 0 || N > a.chunk) {   // (an env of one chunk stays staged for every pass)
-        MOOG_RS_SYNC();
-        MOOG_RS_EACH_LANE
-          for (int32_t j = lane; j < nc; j += MOOG_RS_LANES) moog_rs_stage(a, s, f, lds, e0 + j, j, ox, oy);
-        MOOG_RS_SYNC();
+        MOOG_WAVE_SYNC();
+        MOOG_WAVE_EACH_LANE
+          for (int32_t j = lane; j < nc; j += MOOG_WAVE_LANES) moog_rs_stage(a, s, f, lds, e0 + j, j, ox, oy);
+        MOOG_WAVE_SYNC();
       }
-      MOOG_RS_EACH_LANE {
+      MOOG_WAVE_EACH_LANE {
         if (ray0 + lane / G < R)
           for (int32_t j = lane & (G - 1); j < nc; j += G)
-            moog_rs_test(lds.edge[j], lds.key[j], dx[MOOG_RS_P], dy[MOOG_RS_P], s.max_range, bt[MOOG_RS_P], bk[MOOG_RS_P]);
+            moog_rs_test(lds.edge[j], lds.key[j], dx[MOOG_WAVE_P], dy[MOOG_WAVE_P], s.max_range, bt[MOOG_WAVE_P], bk[MOOG_WAVE_P]);
       }
     }
     for (int32_t m = G >> 1; m; m >>= 1) {   // the lexicographic min over a ray's G lanes
-      MOOG_RS_EACH_LANE { ot[MOOG_RS_P] = MOOG_RS_SHFL_XOR(bt, m); ok[MOOG_RS_P] = MOOG_RS_SHFL_XOR(bk, m); }
-      MOOG_RS_EACH_LANE
-        if (moog_rs_before(ot[MOOG_RS_P], ok[MOOG_RS_P], bt[MOOG_RS_P], bk[MOOG_RS_P])) { bt[MOOG_RS_P] = ot[MOOG_RS_P]; bk[MOOG_RS_P] = ok[MOOG_RS_P]; }
+      MOOG_WAVE_EACH_LANE { ot[MOOG_WAVE_P] = MOOG_WAVE_SHFL_XOR(bt, m); ok[MOOG_WAVE_P] = MOOG_WAVE_SHFL_XOR(bk, m); }
+      MOOG_WAVE_EACH_LANE
+        if (moog_rs_before(ot[MOOG_WAVE_P], ok[MOOG_WAVE_P], bt[MOOG_WAVE_P], bk[MOOG_WAVE_P])) { bt[MOOG_WAVE_P] = ot[MOOG_WAVE_P]; bk[MOOG_WAVE_P] = ok[MOOG_WAVE_P]; }
     }
-    MOOG_RS_EACH_LANE {
+    MOOG_WAVE_EACH_LANE {
       const int32_t ray = ray0 + lane / G;
       if ((lane & (G - 1)) == 0 && ray < R) {
-        const bool hit = bk[MOOG_RS_P] != MOOG_RS_NO_KEY;
-        lds.res[2 * ray] = moog_rs_cast(hit ? bt[MOOG_RS_P] + 0.0 : s.max_range, s.dtype);
-        lds.res[2 * ray + 1] = moog_rs_cast(hit ? (double)(bk[MOOG_RS_P] >> 16) : 0.0, s.dtype);
+        const bool hit = bk[MOOG_WAVE_P] != MOOG_RS_NO_KEY;
+        lds.res[2 * ray] = moog_rs_cast(hit ? bt[MOOG_WAVE_P] + 0.0 : s.max_range, s.dtype);
+        lds.res[2 * ray + 1] = moog_rs_cast(hit ? (double)(bk[MOOG_WAVE_P] >> 16) : 0.0, s.dtype);
       }
     }
   }
-  MOOG_RS_SYNC();
-  MOOG_RS_EACH_LANE {
+  MOOG_WAVE_SYNC();
+  MOOG_WAVE_EACH_LANE {
     if (s.dtype == MOOG_TABLE_F32) {
       uint32_t* out = (uint32_t*)s.out + env * (2 * R);
-      for (int32_t j = lane; j < 2 * R; j += MOOG_RS_LANES) out[j] = lds.res[j];
+      for (int32_t j = lane; j < 2 * R; j += MOOG_WAVE_LANES) out[j] = lds.res[j];
     } else {
       uint32_t* out = (uint32_t*)s.out + env * R;
-      for (int32_t j = lane; j < R; j += MOOG_RS_LANES) out[j] = lds.res[2 * j] | (lds.res[2 * j + 1] << 16);
+      for (int32_t j = lane; j < R; j += MOOG_WAVE_LANES) out[j] = lds.res[2 * j] | (lds.res[2 * j + 1] << 16);
     }
   }
 }

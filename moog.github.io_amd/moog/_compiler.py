@@ -41,6 +41,16 @@ Compiled = collections.namedtuple(
 # observer_key: the first PILRenderer's key, or None when the config has
 # none (the program's render is then 0 x 0: no frames).
 
+# The observer kinds the engine evaluates beside the program, in the order they are lowered: (class, Compiled's list field,
+# Compiled's rows field, the most of them a config may hold, that limit's name in include/moog_engine.h).  Each class has
+# `lower(program, layer_names) -> (descriptor, rows)`.
+OBSERVER_KINDS = (
+    (observers_lib.SpriteTable, 'tables', 'table_rows', _abi.MOOG_MAX_TABLES, 'MOOG_MAX_TABLES'),
+    (observers_lib.RaySensor, 'sensors', 'sensor_rows', _abi.MOOG_MAX_SENSORS, 'MOOG_MAX_SENSORS'),
+    (observers_lib.Contacts, 'contacts', 'contact_rows', _abi.MOOG_MAX_CONTACTS, 'MOOG_MAX_CONTACTS'),
+    (observers_lib.Segmentation, 'segmentations', 'segmentation_rows', _abi.MOOG_MAX_SEGMENTATIONS, 'MOOG_MAX_SEGMENTATIONS'),
+)
+
 
 class _ShapeTable(object):
     def __init__(self, program):
@@ -1373,27 +1383,17 @@ def compile_config(state_initializer, physics, task, action_space, observers, ga
     obs_items = list(observers.items()) if observers else []
     renderers = [(k, o) for k, o in obs_items if isinstance(o, observers_lib.PILRenderer)]
     others = [o for _, o in obs_items
-              if not isinstance(o, (observers_lib.PILRenderer, observers_lib.RawState, observers_lib.SpriteTable,
-                                    observers_lib.Segmentation, observers_lib.RaySensor, observers_lib.Contacts))]
+              if not isinstance(o, (observers_lib.PILRenderer, observers_lib.RawState) + tuple(k[0] for k in OBSERVER_KINDS))]
     if others:
         raise NotImplementedError('observers other than PILRenderer, RawState, SpriteTable, Segmentation, RaySensor and Contacts are not lowered (%s)'
                                   % (', '.join(sorted(set(type(o).__name__ for o in others))),))
-    table_items = [(k, o) for k, o in obs_items if isinstance(o, observers_lib.SpriteTable)]
-    if len(table_items) > _abi.MOOG_MAX_TABLES:
-        raise NotImplementedError('at most %d SpriteTable observers per config (MOOG_MAX_TABLES), got %d'
-                                  % (_abi.MOOG_MAX_TABLES, len(table_items)))
-    sensor_items = [(k, o) for k, o in obs_items if isinstance(o, observers_lib.RaySensor)]
-    if len(sensor_items) > _abi.MOOG_MAX_SENSORS:
-        raise NotImplementedError('at most %d RaySensor observers per config (MOOG_MAX_SENSORS), got %d'
-                                  % (_abi.MOOG_MAX_SENSORS, len(sensor_items)))
-    contact_items = [(k, o) for k, o in obs_items if isinstance(o, observers_lib.Contacts)]
-    if len(contact_items) > _abi.MOOG_MAX_CONTACTS:
-        raise NotImplementedError('at most %d Contacts observers per config (MOOG_MAX_CONTACTS), got %d'
-                                  % (_abi.MOOG_MAX_CONTACTS, len(contact_items)))
-    seg_items = [(k, o) for k, o in obs_items if isinstance(o, observers_lib.Segmentation)]
-    if len(seg_items) > _abi.MOOG_MAX_SEGMENTATIONS:
-        raise NotImplementedError('at most %d Segmentation observers per config (MOOG_MAX_SEGMENTATIONS), got %d'
-                                  % (_abi.MOOG_MAX_SEGMENTATIONS, len(seg_items)))
+    kind_items = {}   # Compiled's list field -> [(key, observer)] of that kind, in dict order
+    for cls, field, _, limit, limit_name in OBSERVER_KINDS:
+        kind_items[field] = [(k, o) for k, o in obs_items if isinstance(o, cls)]
+        if len(kind_items[field]) > limit:
+            raise NotImplementedError('at most %d %s observers per config (%s), got %d'
+                                      % (limit, cls.__name__, limit_name, len(kind_items[field])))
+    seg_items = kind_items['segmentations']
     if seg_items and not renderers:
         # (a config without a PILRenderer lowers to a program that draws no frames: its engine has no raster state and takes
         #  no views; a Segmentation there is refused for now, not ruled out -- DESIGN 8)
@@ -1485,38 +1485,31 @@ def compile_config(state_initializer, physics, task, action_space, observers, ga
     # rule_ref_index: program rule -> index of the config's rule object it stands for in a pre-order walk of the config's
     # rule forest (-1: a rule the lowering added: the extra parts of an expanded config-local rule, state slots of forces)
     # pstate_slots: (attribute of the initializer's object kept across episodes, rule slot that holds it per env)
-    c = Compiled(P, layer_names, layer_slots, obs_key, _abi.layout_of(P), [],
-                 rule_ref_index + [-1] * (int(P.n_rules) - len(rule_ref_index)), sorted(pstate_slot.items()),
-                 # (slot, metadata key, cell that holds the look-ahead's exit, {exit: value}) of the metadata values
-                 # an initializer's look-ahead decides
-                 [(slot_of[id(sp)], key, cell, table) for sp, key, cell, table in getattr(tr, 'dynamic_meta', [])
-                  if id(sp) in slot_of],
-                 # PILRenderer(color_to_rgb=<a callable>): evaluated on the host (environment.py _refresh_colors)
-                 color_fn, layer_n_init, views, [], {}, [], {}, [], {}, [], {})
-    # SpriteTables read the finished layout (rows = the slots of their layers) and leave the program alone
-    for key, o in table_items:
-        T, rows = o.lower(P, layer_names)
-        c.tables.append((key, T))
-        c.table_rows[key] = rows
-    # RaySensors likewise (rows, the origin's slot)
-    for key, o in sensor_items:
-        T, rows = o.lower(P, layer_names)
-        c.sensors.append((key, T))
-        c.sensor_rows[key] = rows
-    # Contacts too (two row lists)
-    for key, o in contact_items:
-        T, rows = o.lower(P, layer_names)
-        c.contacts.append((key, T))
-        c.contact_rows[key] = rows
-    # Segmentations read the finished layout too (ids per sprite slot); whether the mask rasteriser can hold such a frame
-    # (moog_engine_raster_path's criteria) is checked here, so that the refusal comes when the config is lowered
-    for key, o in seg_items:
-        G, rows = o.lower(P, layer_names)
-        why = segmentation_refusal(P, c.layout, G)
-        if why:
-            raise NotImplementedError('Segmentation observer %r: %s' % (key, why))
-        c.segmentations.append((key, G))
-        c.segmentation_rows[key] = rows
+    c = Compiled(
+        program=P, layer_names=layer_names, layer_slots=layer_slots, observer_key=obs_key, layout=_abi.layout_of(P),
+        shape_names=[], rule_ref_index=rule_ref_index + [-1] * (int(P.n_rules) - len(rule_ref_index)),
+        pstate_slots=sorted(pstate_slot.items()),
+        # (slot, metadata key, cell that holds the look-ahead's exit, {exit: value}) of the metadata values
+        # an initializer's look-ahead decides
+        dynamic_meta=[(slot_of[id(sp)], key, cell, table) for sp, key, cell, table in getattr(tr, 'dynamic_meta', [])
+                      if id(sp) in slot_of],
+        # PILRenderer(color_to_rgb=<a callable>): evaluated on the host (environment.py _refresh_colors)
+        color_fn=color_fn, layer_n_init=layer_n_init, views=views,
+        tables=[], table_rows={}, segmentations=[], segmentation_rows={}, sensors=[], sensor_rows={}, contacts=[],
+        contact_rows={})
+    # The observers of OBSERVER_KINDS read the finished layout (rows = the slots of their layers; a RaySensor the origin's slot
+    # too, a Contacts observer two row lists, a Segmentation ids per sprite slot) and leave the program alone.
+    for cls, field, rows_field, _, _ in OBSERVER_KINDS:
+        for key, o in kind_items[field]:
+            T, rows = o.lower(P, layer_names)
+            if cls is observers_lib.Segmentation:
+                # whether the mask rasteriser can hold such a frame (moog_engine_raster_path's criteria) is checked here, so
+                # that the refusal comes when the config is lowered
+                why = segmentation_refusal(P, c.layout, T)
+                if why:
+                    raise NotImplementedError('Segmentation observer %r: %s' % (key, why))
+            getattr(c, field).append((key, T))
+            getattr(c, rows_field)[key] = rows
     # shape id -> Sprite.shape value (sprite.py:517-523): the name, or 'custom' for raw vertices
     c.shape_names.extend(k[1] if k[0] == 'name' else 'custom' for k, _ in shapes.entries)
     return c

@@ -24,6 +24,29 @@ from . import _abi
 from . import _compiler
 from . import _dm_env as dm_env
 from . import _engine
+from .observers import contacts as contacts_lib, ray_sensor, segmentation, sprite_table
+
+# How an observer goes from a lowered config to the engine, kind by kind, in the order they are attached.  field: Compiled's
+# [(key, descriptor)]; add / bind: the engine's functions that take the descriptor and the tensor; tensors: the env's dict
+# that holds the tensor under the observer's key; index: the env's dict {key: engine index}; observe: the engine's function
+# that refreshes every bound observer of the kind, None for the kinds drawn with the frames; spec: descriptor -> specs.Array
+# of one env's observation.
+ObserverKind = collections.namedtuple('ObserverKind', ['field', 'add', 'bind', 'tensors', 'index', 'observe', 'spec'])
+OBSERVER_KINDS = (
+    ObserverKind('views', 'moog_engine_add_view', 'moog_engine_set_view_image', 'view_images', '_view_index', None,
+                 lambda R: dm_env.specs.Array(shape=(int(R.height), int(R.width), 3), dtype=np.uint8)),
+    ObserverKind('tables', 'moog_engine_add_table', 'moog_engine_set_table_buffer', 'tables', '_table_index',
+                 'moog_engine_observe_tables', sprite_table.table_spec),
+    ObserverKind('sensors', 'moog_engine_add_sensor', 'moog_engine_set_sensor_buffer', 'tables', '_sensor_index',
+                 'moog_engine_observe_sensors', ray_sensor.sensor_spec),
+    ObserverKind('contacts', 'moog_engine_add_contacts', 'moog_engine_set_contacts_buffer', 'tables', '_contacts_index',
+                 'moog_engine_observe_contacts', contacts_lib.contacts_spec),
+    ObserverKind('segmentations', 'moog_engine_add_segmentation', 'moog_engine_set_segmentation_image', 'view_images',
+                 '_segmentation_index', None, segmentation.segmentation_spec),
+)
+# The tensors a SubBatchedEnvironment hands a part: slices of its own.
+PartBuffers = collections.namedtuple('PartBuffers', ['state_f64', 'state_i32', 'reward', 'discount', 'step_type', 'image',
+                                                     'view_images', 'repeat_count', 'tables'])
 
 _FAULT_EXC = (
     (_abi.MOOG_FAULT_SAMPLER_EXHAUSTED, RecursionError,
@@ -112,10 +135,8 @@ class BatchedEnvironment(object):
         self.layout = L
         n = self.num_envs
         if _buffers is not None:
-            (self.state_f64, self.state_i32, self.reward, self.discount, self.step_type, self.image) = _buffers[:6]
-            self.view_images = _buffers[6] if len(_buffers) > 6 else None
-            self.repeat_count = _buffers[7] if len(_buffers) > 7 else None
-            self.tables = _buffers[8] if len(_buffers) > 8 else None
+            for name in PartBuffers._fields:
+                setattr(self, name, getattr(_buffers, name))
         else:
             with torch.cuda.device(self.device):
                 (self.state_f64, self.state_i32, self.reward, self.discount, self.step_type,
@@ -138,24 +159,10 @@ class BatchedEnvironment(object):
         if self.compiled.observer_key is not None:
             self._frames[self.compiled.observer_key] = self.image
         self._frames.update(self.view_images)
-        self._handle = ctypes.c_void_p()
         if self._specialize:
             from . import _spec
             _spec.build(P)
-        dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        with torch.cuda.device(self.device):   # (the engine calls hipSetDevice: keep torch's current device)
-            _engine.check(self._lib, self._lib.moog_engine_create(
-                ctypes.byref(P), n, dev_index, int(seed), int(env_index0),
-                ctypes.byref(self._handle)))
-        view = _abi.StateView()
-        view.f64 = ctypes.cast(self.state_f64.data_ptr(), ctypes.POINTER(ctypes.c_double))
-        view.i32 = ctypes.cast(self.state_i32.data_ptr(), ctypes.POINTER(ctypes.c_int32))
-        _engine.check(self._lib, self._lib.moog_engine_load_state(self._handle, ctypes.byref(view)))
-        self._attach_views()
-        self._attach_tables()
-        self._attach_sensors()
-        self._attach_contacts()
-        self._attach_segmentations()
+        self._open_engine()
         self._out = _abi.StepOut()
         self._out.reward = ctypes.cast(self.reward.data_ptr(), ctypes.POINTER(ctypes.c_double))
         self._out.discount = ctypes.cast(self.discount.data_ptr(), ctypes.POINTER(ctypes.c_double))
@@ -214,70 +221,42 @@ class BatchedEnvironment(object):
         self._action_repeat = self._check_action_repeat(k)
         self._apply_action_repeat()
 
-    def _attach_views(self):
-        """The config's PILRenderers after the first: an extra view of the engine each (moog_engine_add_view), drawing into
-        its own tensor whenever the primary's frames are drawn."""
-        self._view_index = {}
-        for key, render in self.compiled.views:
-            idx = ctypes.c_int32()
-            with self._torch.cuda.device(self.device):
-                _engine.check(self._lib, self._lib.moog_engine_add_view(self._handle, ctypes.byref(render), ctypes.byref(idx)))
-            _engine.check(self._lib, self._lib.moog_engine_set_view_image(
-                self._handle, idx.value, ctypes.c_void_p(self.view_images[key].data_ptr())))
-            self._view_index[key] = idx.value
+    def _open_engine(self):
+        """A new engine handle over `self.compiled` and the records as they are: create, load_state, and the config's
+        observers attached (the constructor; _grow_layers, over the new program and the moved records)."""
+        torch = self._torch
+        self._handle = ctypes.c_void_p()
+        dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        with torch.cuda.device(self.device):   # (the engine calls hipSetDevice: keep torch's current device)
+            _engine.check(self._lib, self._lib.moog_engine_create(
+                ctypes.byref(self.compiled.program), self.num_envs, dev_index, self._seed, self._env_index0,
+                ctypes.byref(self._handle)))
+        view = _abi.StateView()
+        view.f64 = ctypes.cast(self.state_f64.data_ptr(), ctypes.POINTER(ctypes.c_double))
+        view.i32 = ctypes.cast(self.state_i32.data_ptr(), ctypes.POINTER(ctypes.c_int32))
+        _engine.check(self._lib, self._lib.moog_engine_load_state(self._handle, ctypes.byref(view)))
+        self._attach_observers()
 
-    def _attach_segmentations(self):
-        """The config's Segmentation observers: a segmentation of the engine each (moog_engine_add_segmentation), drawn into
-        its own tensor (kept beside the extra views' frames, `view_images`) whenever the primary's frames are drawn."""
-        self._segmentation_index = {}
-        for key, seg in self.compiled.segmentations:
-            idx = ctypes.c_int32()
-            with self._torch.cuda.device(self.device):
-                _engine.check(self._lib, self._lib.moog_engine_add_segmentation(self._handle, ctypes.byref(seg), ctypes.byref(idx)))
-            _engine.check(self._lib, self._lib.moog_engine_set_segmentation_image(
-                self._handle, idx.value, ctypes.c_void_p(self.view_images[key].data_ptr())))
-            self._segmentation_index[key] = idx.value
+    def _attach_observers(self):
+        """Every observer of OBSERVER_KINDS in the config: described to the engine (its add function), bound to its own tensor
+        (its bind function), and its engine index kept under its key.  An extra view and a segmentation are drawn whenever
+        the primary's frames are; a sprite table, a ray sensor and a contacts observer are written by every reset / step call
+        and by observation()."""
+        for kind in OBSERVER_KINDS:
+            index = {}
+            for key, desc in getattr(self.compiled, kind.field):
+                idx = ctypes.c_int32()
+                with self._torch.cuda.device(self.device):
+                    _engine.check(self._lib, getattr(self._lib, kind.add)(self._handle, ctypes.byref(desc), ctypes.byref(idx)))
+                _engine.check(self._lib, getattr(self._lib, kind.bind)(
+                    self._handle, idx.value, ctypes.c_void_p(getattr(self, kind.tensors)[key].data_ptr())))
+                index[key] = idx.value
+            setattr(self, kind.index, index)
 
     def segmentation_rows(self, key):
         """[(layer name, index in layer)] for every row of the Segmentation observer `key`: value v of an 'instance' mask is
         row v - 1 (the rows of a SpriteTable over the same layers); value v of a 'layer' mask is the v-th chosen layer."""
         return list(self.compiled.segmentation_rows[key])
-
-    def _attach_tables(self):
-        """The config's SpriteTables: a sprite table of the engine each (moog_engine_add_table), written into its own tensor
-        by every reset / step call and by observation()."""
-        self._table_index = {}
-        for key, table in self.compiled.tables:
-            idx = ctypes.c_int32()
-            with self._torch.cuda.device(self.device):
-                _engine.check(self._lib, self._lib.moog_engine_add_table(self._handle, ctypes.byref(table), ctypes.byref(idx)))
-            _engine.check(self._lib, self._lib.moog_engine_set_table_buffer(
-                self._handle, idx.value, ctypes.c_void_p(self.tables[key].data_ptr())))
-            self._table_index[key] = idx.value
-
-    def _attach_sensors(self):
-        """The config's RaySensors: a ray sensor of the engine each (moog_engine_add_sensor), cast into its own tensor (kept
-        beside the tables' tensors, `tables`) by every reset / step call and by observation()."""
-        self._sensor_index = {}
-        for key, sensor in self.compiled.sensors:
-            idx = ctypes.c_int32()
-            with self._torch.cuda.device(self.device):
-                _engine.check(self._lib, self._lib.moog_engine_add_sensor(self._handle, ctypes.byref(sensor), ctypes.byref(idx)))
-            _engine.check(self._lib, self._lib.moog_engine_set_sensor_buffer(
-                self._handle, idx.value, ctypes.c_void_p(self.tables[key].data_ptr())))
-            self._sensor_index[key] = idx.value
-
-    def _attach_contacts(self):
-        """The config's Contacts observers: a contacts observer of the engine each (moog_engine_add_contacts), evaluated into
-        its own uint8 tensor (kept beside the tables' tensors, `tables`) by every reset / step call and by observation()."""
-        self._contacts_index = {}
-        for key, desc in self.compiled.contacts:
-            idx = ctypes.c_int32()
-            with self._torch.cuda.device(self.device):
-                _engine.check(self._lib, self._lib.moog_engine_add_contacts(self._handle, ctypes.byref(desc), ctypes.byref(idx)))
-            _engine.check(self._lib, self._lib.moog_engine_set_contacts_buffer(
-                self._handle, idx.value, ctypes.c_void_p(self.tables[key].data_ptr())))
-            self._contacts_index[key] = idx.value
 
     def contact_rows(self, key):
         """(rows_0, rows_1) of the Contacts observer `key`: [(layer name, index in layer)] for every row of each argument --
@@ -297,30 +276,27 @@ class BatchedEnvironment(object):
         return np.array([[T.dirs[k][0], T.dirs[k][1]] for k in range(int(T.n_rays))], dtype=np.float64)
 
     def _observe_tables(self):
-        if self.compiled.tables:
-            with self._torch.cuda.device(self.device):
-                _engine.check(self._lib, self._lib.moog_engine_observe_tables(self._handle, self._stream()))
-        if self.compiled.sensors:
-            with self._torch.cuda.device(self.device):
-                _engine.check(self._lib, self._lib.moog_engine_observe_sensors(self._handle, self._stream()))
-        if self.compiled.contacts:
-            with self._torch.cuda.device(self.device):
-                _engine.check(self._lib, self._lib.moog_engine_observe_contacts(self._handle, self._stream()))
+        for kind in OBSERVER_KINDS:
+            if kind.observe and getattr(self.compiled, kind.field):
+                with self._torch.cuda.device(self.device):
+                    _engine.check(self._lib, getattr(self._lib, kind.observe)(self._handle, self._stream()))
+
+    @staticmethod
+    def _allocate_observer_buffers(torch, compiled, n, device, tensors):
+        """{key: zeros [n] + the observer's spec} for the observers of the kinds kept in the dict `tensors`, kind after kind."""
+        bufs = {}
+        for kind in OBSERVER_KINDS:
+            if kind.tensors == tensors:
+                for key, desc in getattr(compiled, kind.field):
+                    spec = kind.spec(desc)
+                    bufs[key] = torch.zeros((n,) + tuple(spec.shape), dtype=getattr(torch, spec.dtype.name), device=device)
+        return bufs
 
     @staticmethod
     def allocate_table_buffers(torch, compiled, n, device):
         """{key: float32 / float16 [n, rows, columns]} for the config's SpriteTables and {key: float32 / float16
         [n, rays, 2]} for its RaySensors and {key: uint8 [n, R0, R1] or [n, R0, layers]} for its Contacts observers."""
-        from .observers import contacts as contacts_lib
-        bufs = {key: torch.zeros((n, int(T.n_rows), int(T.n_cols)), device=device,
-                                 dtype=torch.float16 if T.dtype == _abi.MOOG_TABLE_F16 else torch.float32)
-                for key, T in compiled.tables}
-        bufs.update({key: torch.zeros((n, int(T.n_rays), 2), device=device,
-                                      dtype=torch.float16 if T.dtype == _abi.MOOG_TABLE_F16 else torch.float32)
-                     for key, T in compiled.sensors})
-        bufs.update({key: torch.zeros((n,) + contacts_lib.contacts_shape(T), device=device, dtype=torch.uint8)
-                     for key, T in compiled.contacts})
-        return bufs
+        return BatchedEnvironment._allocate_observer_buffers(torch, compiled, n, device, 'tables')
 
     def table_rows(self, key):
         """[(layer name, index in layer)] for every row of the SpriteTable observer `key`."""
@@ -336,11 +312,7 @@ class BatchedEnvironment(object):
     def allocate_view_buffers(torch, compiled, n, device):
         """{key: uint8 [n, H, W, 3]} for the extra views (the config's PILRenderers after the first) and {key: uint8
         [n, H, W]} for its Segmentation observers."""
-        bufs = {key: torch.zeros((n, int(R.height), int(R.width), 3), dtype=torch.uint8, device=device)
-                for key, R in compiled.views}
-        bufs.update({key: torch.zeros((n, int(G.height), int(G.width)), dtype=torch.uint8, device=device)
-                     for key, G in compiled.segmentations})
-        return bufs
+        return BatchedEnvironment._allocate_observer_buffers(torch, compiled, n, device, 'view_images')
 
     def _setup_color_fn(self):
         """PILRenderer(color_to_rgb=<a callable>): the callable is evaluated here, on the host, once per distinct colour
@@ -696,25 +668,15 @@ class BatchedEnvironment(object):
             new_q = move(self.state_i32, src_q, torch.int32)
             # the new engine, over the new records (outputs stay where they are)
             had_schedule, f32 = self._perm is not None, self._action_f32
-            self._lib.moog_engine_destroy(self._handle)
-            self._handle = ctypes.c_void_p()
+            self.close()
             self.compiled, self.layout = new_c, L
             self.state_f64, self.state_i32 = new_f, new_q
-            dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-            _engine.check(self._lib, self._lib.moog_engine_create(
-                ctypes.byref(P), self.num_envs, dev_index, self._seed, self._env_index0, ctypes.byref(self._handle)))
-            view = _abi.StateView()
-            view.f64 = ctypes.cast(self.state_f64.data_ptr(), ctypes.POINTER(ctypes.c_double))
-            view.i32 = ctypes.cast(self.state_i32.data_ptr(), ctypes.POINTER(ctypes.c_int32))
-            _engine.check(self._lib, self._lib.moog_engine_load_state(self._handle, ctypes.byref(view)))
-            self._attach_views()
-            # (other capacities, other row counts: new tensors, filled from the records that have just moved over)
+            # (other capacities, other row counts: new tensors for the tables, sensors and contacts -- their rows and ids move
+            #  -- filled from the records that have just moved over, the readings under the new ids at once; the views' and
+            #  segmentations' tensors keep their size)
             self.tables = self.allocate_table_buffers(torch, new_c, self.num_envs, self.device)
-            self._attach_tables()
-            self._attach_sensors()   # (other capacities, other rows and ids; the readings under them at once)
-            self._attach_contacts()  # (the rows move: new descriptors over the new tensors)
+            self._open_engine()
             self._observe_tables()
-            self._attach_segmentations()   # (other capacities, other ids; the tensors keep their size)
             if f32:
                 _engine.check(self._lib, self._lib.moog_engine_set_action_dtype(self._handle, 1))
             self._apply_action_repeat()
@@ -920,7 +882,6 @@ class BatchedEnvironment(object):
 
     def _check_record(self, record):
         """rollout()'s `record` as a list of SpriteTable keys, or the reason it cannot be recorded (no device needed)."""
-        from .observers import sprite_table
         keys = [record] if isinstance(record, str) else list(record)
         if not keys:
             raise ValueError('rollout: record is empty: name at least one SpriteTable observer of the config (or pass None)')
@@ -1105,11 +1066,12 @@ class BatchedEnvironment(object):
         return self._observation()
 
     def observation_spec(self):
-        from .observers import contacts as contacts_lib, raw_state, sprite_table
-        tables = dict(self.compiled.tables)   # (a SpriteTable's shape follows from this environment's layer capacities)
-        contacts = dict(self.compiled.contacts)   # (a Contacts observer's too)
-        return {k: sprite_table.table_spec(tables[k]) if k in tables
-                else contacts_lib.contacts_spec(contacts[k]) if k in contacts else o.observation_spec()
+        from .observers import raw_state
+        # (a SpriteTable's shape follows from this environment's layer capacities, a Contacts observer's too: the specs of the
+        #  lowered kinds come from their descriptors.  A PILRenderer states its own, the reference's image_size + (3,).)
+        lowered = {key: kind.spec(desc) for kind in OBSERVER_KINDS if kind.field != 'views'
+                   for key, desc in getattr(self.compiled, kind.field)}
+        return {k: lowered[k] if k in lowered else o.observation_spec()
                 for k, o in self.observers.items() if not isinstance(o, raw_state.RawState)}
 
     def action_spec(self):
@@ -1309,9 +1271,9 @@ class SubBatchedEnvironment(object):
         self.part_envs = m
         self.parts = []
         for g in range(G):
-            views = tuple(b[g * m:(g + 1) * m] for b in bufs) + (
-                {k: t[g * m:(g + 1) * m] for k, t in self.view_images.items()}, self.repeat_count[g * m:(g + 1) * m],
-                {k: t[g * m:(g + 1) * m] for k, t in self.tables.items()})
+            part = slice(g * m, (g + 1) * m)
+            views = PartBuffers(*(b[part] for b in bufs), view_images={k: t[part] for k, t in self.view_images.items()},
+                                repeat_count=self.repeat_count[part], tables={k: t[part] for k, t in self.tables.items()})
             self.parts.append(BatchedEnvironment(
                 state_initializer, physics, task, action_space, observers, game_rules, None,
                 num_envs=m, device=self.device, seed=seed, env_index0=int(env_index0) + g * m,

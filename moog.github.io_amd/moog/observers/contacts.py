@@ -46,6 +46,7 @@ import numpy as np
 
 from .. import _abi
 from .. import _dm_env as dm_env
+from . import _rows
 
 MODES = {'pair': _abi.MOOG_CONTACTS_PAIR, 'layer': _abi.MOOG_CONTACTS_LAYER}
 
@@ -60,9 +61,7 @@ def _layer_tuple(arg, what):
     for name in arg:
         if not isinstance(name, str):
             raise ValueError('Contacts: %s is a layer name or a tuple of names, got %r' % (what, arg))
-    if len(set(arg)) != len(arg):
-        raise ValueError('Contacts: a layer is named twice in %s=%r' % (what, arg))
-    return arg
+    return _rows.check_layers('Contacts', arg, what)
 
 
 def contacts_layers(contacts):
@@ -107,33 +106,18 @@ class Contacts(object):
     def visible_only(self):
         return self._visible_only
 
-    @staticmethod
-    def _rows(program, layer_names, names, what, every_layer_has_a_slot):
-        slots, rows = [], []
-        for name in names:
-            if name not in layer_names:
-                raise ValueError('Contacts: unknown layer %r in %s (the state has %s)' % (name, what, ', '.join(layer_names)))
-            li = layer_names.index(name)
-            s0, n = int(program.layer_slot0[li]), int(program.layer_nslots[li])
-            if n == 0 and every_layer_has_a_slot:
-                raise ValueError("Contacts: layer %r of %s holds no sprite slot: its column of a mode='layer' tensor could "
-                                 'never be set' % (name, what))
-            for k in range(n):
-                slots.append(s0 + k)
-                rows.append((name, k))
-        if not rows:
-            raise ValueError('Contacts: the layers of %s hold no sprite slot (0 rows)' % (what,))
-        if len(rows) > _abi.MOOG_MAX_SLOTS:
-            raise ValueError('Contacts: %s has %d rows, more than %d (MOOG_MAX_SLOTS)' % (what, len(rows), _abi.MOOG_MAX_SLOTS))
-        return slots, rows
-
     def lower(self, program, layer_names):
         """(_abi.Contacts, (rows_0, rows_1)) of this observer over a lowered program: each rows list is [(layer name, index in
         layer)] per row, the rows of `SpriteTable(layers=...).lower`."""
         layer_names = list(layer_names)
-        layer_mode = self._mode == 'layer'
-        slots_0, rows_0 = self._rows(program, layer_names, self._layers_0, 'layers_0', False)
-        slots_1, rows_1 = self._rows(program, layer_names, self.layers_1, 'layers_1', layer_mode)
+        slots_0, rows_0 = _rows.layer_rows('Contacts', program, layer_names, self._layers_0, 'layers_0')
+        slots_1, rows_1 = _rows.layer_rows('Contacts', program, layer_names, self.layers_1, 'layers_1')
+        with_rows_1 = [name for name in self.layers_1 if (name, 0) in rows_1]
+        if self._mode == 'layer':
+            for name in self.layers_1:
+                if name not in with_rows_1:
+                    raise ValueError("Contacts: layer %r of layers_1 holds no sprite slot: its column of a mode='layer' tensor "
+                                     'could never be set' % (name,))
         T = _abi.Contacts()
         T.n_rows_0, T.n_rows_1 = len(rows_0), len(rows_1)
         T.flags = _abi.MOOG_CONTACTS_VISIBLE_ONLY if self._visible_only else 0
@@ -142,7 +126,7 @@ class Contacts(object):
             T.row_slot_0[k] = s
         for k, s in enumerate(slots_1):
             T.row_slot_1[k] = s
-        T._n_layers_1 = len([name for name in self.layers_1 if int(program.layer_nslots[layer_names.index(name)]) > 0])
+        T._n_layers_1 = len(with_rows_1)
         self._lowered = T
         return T, (rows_0, rows_1)
 

@@ -27,15 +27,15 @@ import numpy as np
 
 from .. import _abi
 from .. import _dm_env as dm_env
+from . import _rows
 
 MODES = {'instance': _abi.MOOG_SENSOR_INSTANCE, 'layer': _abi.MOOG_SENSOR_LAYER}
-_DTYPES = {'float32': _abi.MOOG_TABLE_F32, 'float16': _abi.MOOG_TABLE_F16}
 FLOAT16_MAX = 65504.0
 
 
 def sensor_dtype(sensor):
     """numpy dtype of a lowered sensor (_abi.Sensor)."""
-    return np.dtype(np.float16 if sensor.dtype == _abi.MOOG_TABLE_F16 else np.float32)
+    return _rows.numpy_dtype(sensor.dtype)
 
 
 def sensor_spec(sensor, name=None):
@@ -52,8 +52,6 @@ class RaySensor(object):
         'float16'."""
         if not isinstance(origin_layer, str):
             raise ValueError('RaySensor: origin_layer is a layer name, got %r' % (origin_layer,))
-        if isinstance(layers, str):
-            raise ValueError('RaySensor: layers is a tuple of names, not one string')
         if isinstance(origin_index, bool) or int(origin_index) != origin_index or origin_index < 0:
             raise ValueError('RaySensor: origin_index must be a non-negative integer, got %r' % (origin_index,))
         if isinstance(num_rays, bool) or int(num_rays) != num_rays or not 1 <= num_rays <= _abi.MOOG_MAX_RAYS:
@@ -68,17 +66,10 @@ class RaySensor(object):
             raise ValueError('RaySensor: max_range must be finite and above 0, got %r' % (max_range,))
         if mode not in MODES:
             raise ValueError("RaySensor: unknown mode %r (modes are 'instance' and 'layer')" % (mode,))
-        try:
-            dtype = np.dtype(dtype).name
-        except TypeError:
-            dtype = repr(dtype)
-        if dtype not in _DTYPES:
-            raise ValueError("RaySensor: dtype must be 'float32' or 'float16', got %s" % (dtype,))
+        dtype = _rows.check_dtype('RaySensor', dtype)
         if dtype == 'float16' and max_range > FLOAT16_MAX:
             raise ValueError('RaySensor: max_range %r is above 65504: the no-hit reading would be inf as float16' % (max_range,))
-        self._layers = None if layers is None else tuple(layers)
-        if self._layers is not None and len(set(self._layers)) != len(self._layers):
-            raise ValueError('RaySensor: a layer is named twice in %r' % (self._layers,))
+        self._layers = None if layers is None else _rows.check_layers('RaySensor', layers)
         self._origin_layer, self._origin_index = origin_layer, int(origin_index)
         self._num_rays, self._fov, self._heading, self._max_range = int(num_rays), fov, heading, max_range
         self._follow_angle, self._visible_only = bool(follow_angle), bool(visible_only)
@@ -118,25 +109,14 @@ class RaySensor(object):
         """(_abi.Sensor, [(layer name, index in layer)] per row) of this observer over a lowered program: the rows are
         `SpriteTable(layers=...).lower`'s."""
         layer_names = list(layer_names)
-        names = layer_names if self._layers is None else list(self._layers)
+        slots, rows = _rows.layer_rows('RaySensor', program, layer_names, self._layers)
+        if self._mode == 'instance' and len(rows) > 255:
+            raise NotImplementedError(
+                'RaySensor: more than 255 rows in instance mode (an id is 1 .. 255, 0 is "no hit"): choose fewer '
+                "layers, or mode='layer'")
         T = _abi.Sensor()
-        rows = []
-        for name in names:
-            if name not in layer_names:
-                raise ValueError('RaySensor: unknown layer %r (the state has %s)' % (name, ', '.join(layer_names)))
-            li = layer_names.index(name)
-            s0, n = int(program.layer_slot0[li]), int(program.layer_nslots[li])
-            for k in range(n):
-                if len(rows) >= _abi.MOOG_MAX_SLOTS:
-                    raise ValueError('RaySensor: more than %d rows' % _abi.MOOG_MAX_SLOTS)
-                if self._mode == 'instance' and len(rows) >= 255:
-                    raise NotImplementedError(
-                        'RaySensor: more than 255 rows in instance mode (an id is 1 .. 255, 0 is "no hit"): choose fewer '
-                        "layers, or mode='layer'")
-                T.row_slot[len(rows)] = s0 + k
-                rows.append((name, k))
-        if not rows:
-            raise ValueError('RaySensor: the chosen layers hold no sprite slot')
+        for k, s in enumerate(slots):
+            T.row_slot[k] = s
         if self._origin_layer not in layer_names:
             raise ValueError('RaySensor: unknown origin_layer %r (the state has %s)'
                              % (self._origin_layer, ', '.join(layer_names)))
@@ -148,7 +128,7 @@ class RaySensor(object):
         T.n_rows, T.n_rays = len(rows), self._num_rays
         T.flags = ((_abi.MOOG_SENSOR_FOLLOW_ANGLE if self._follow_angle else 0)
                    | (_abi.MOOG_SENSOR_VISIBLE_ONLY if self._visible_only else 0))
-        T.mode, T.dtype, T.max_range = MODES[self._mode], _DTYPES[self._dtype], self._max_range
+        T.mode, T.dtype, T.max_range = MODES[self._mode], _rows.DTYPES[self._dtype], self._max_range
         for k in range(self._num_rays):
             T.dirs[k][0], T.dirs[k][1] = float(self._directions[k, 0]), float(self._directions[k, 1])
         return T, rows

@@ -21,6 +21,7 @@ import numpy as np
 
 from .. import _abi
 from .. import _dm_env as dm_env
+from . import _rows
 from . import polygon_modifiers
 
 MODES = ('instance', 'layer')
@@ -38,8 +39,6 @@ class Segmentation(object):
         at most 128.  layers: None (every layer of the state, in its order) or a tuple of layer names, used in the given
         order.  mode: 'instance' or 'layer'.  polygon_modifier: what PILRenderer accepts (DoNothing, TorusGeometry,
         FirstPersonAgent); a torus copy carries its sprite's id."""
-        if isinstance(layers, str):
-            raise ValueError('Segmentation: layers is a tuple of names, not one string')
         self._image_size = tuple(int(v) for v in image_size)
         if len(self._image_size) != 2 or min(self._image_size) < 1:
             raise ValueError('Segmentation: image_size must be two positive integers, got %r' % (image_size,))
@@ -50,9 +49,7 @@ class Segmentation(object):
         if mode not in MODES:
             raise ValueError("Segmentation: unknown mode %r (modes are 'instance' and 'layer')" % (mode,))
         self._mode = mode
-        self._layers = None if layers is None else tuple(layers)
-        if self._layers is not None and len(set(self._layers)) != len(self._layers):
-            raise ValueError('Segmentation: a layer is named twice in %r' % (self._layers,))
+        self._layers = None if layers is None else _rows.check_layers('Segmentation', layers)
         if polygon_modifier is None:
             polygon_modifier = polygon_modifiers.DoNothing()
         if not isinstance(polygon_modifier, (polygon_modifiers.DoNothing, polygon_modifiers.TorusGeometry,
@@ -90,24 +87,13 @@ class Segmentation(object):
             G.polymod, G.polymod_layer = _abi.MOOG_POLYMOD_FIRST_PERSON, layer_names.index(pm._agent_layer)
         else:
             G.polymod = _abi.MOOG_POLYMOD_NONE
-        rows = []
-        for pos, name in enumerate(names):
-            if name not in layer_names:
-                raise ValueError('Segmentation: unknown layer %r (the state has %s)' % (name, ', '.join(layer_names)))
-            li = layer_names.index(name)
-            s0, n = int(program.layer_slot0[li]), int(program.layer_nslots[li])
-            for k in range(n):
-                rows.append((name, k))
-                if self._mode == 'instance':
-                    if len(rows) > 255:
-                        raise NotImplementedError(
-                            'Segmentation: more than 255 rows in instance mode (an id is one byte, 0 is "no sprite"): '
-                            "choose fewer layers, or mode='layer'")
-                    G.slot_id[s0 + k] = len(rows)
-                else:
-                    G.slot_id[s0 + k] = 1 + pos
-        if not rows:
-            raise ValueError('Segmentation: the chosen layers hold no sprite slot')
+        slots, rows = _rows.layer_rows('Segmentation', program, layer_names, self._layers)
+        if self._mode == 'instance' and len(rows) > 255:
+            raise NotImplementedError(
+                'Segmentation: more than 255 rows in instance mode (an id is one byte, 0 is "no sprite"): '
+                "choose fewer layers, or mode='layer'")
+        for r, (s, (name, _)) in enumerate(zip(slots, rows)):
+            G.slot_id[s] = 1 + r if self._mode == 'instance' else 1 + names.index(name)
         return G, rows
 
     def observation_spec(self):

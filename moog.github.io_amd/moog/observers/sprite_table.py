@@ -15,6 +15,7 @@ import numpy as np
 
 from .. import _abi
 from .. import _dm_env as dm_env
+from . import _rows
 
 # column name -> MOOG_TCOL_* (include/moog_engine.h): the numeric Sprite.FACTOR_NAMES, then what the records hold besides
 COLUMN_IDS = {
@@ -25,13 +26,12 @@ COLUMN_IDS = {
     'alive': _abi.MOOG_TCOL_ALIVE, 'layer': _abi.MOOG_TCOL_LAYER, 'shape_id': _abi.MOOG_TCOL_SHAPE_ID,
     'n_vertices': _abi.MOOG_TCOL_N_VERTICES,
 }
-_DTYPES = {'float32': _abi.MOOG_TABLE_F32, 'float16': _abi.MOOG_TABLE_F16}
 NEEDS_SPRITE_FACTORS = ('scale', 'aspect_ratio')
 
 
 def table_dtype(table):
     """numpy dtype of a lowered table (_abi.Table)."""
-    return np.dtype(np.float16 if table.dtype == _abi.MOOG_TABLE_F16 else np.float32)
+    return _rows.numpy_dtype(table.dtype)
 
 
 def table_spec(table, name=None):
@@ -48,9 +48,9 @@ class SpriteTable(object):
         columns: a tuple of names from ALL_COLUMNS (`shape`, a string, and `metadata` are not columns; `shape_id` indexes
         `compiled.shape_names`); `scale` / `aspect_ratio` need an environment built with keep_sprite_factors=True.
         dtype: 'float32' or 'float16'."""
-        if isinstance(layers, str) or isinstance(columns, str):
-            raise ValueError('SpriteTable: layers / columns are tuples of names, not one string')
-        self._layers = None if layers is None else tuple(layers)
+        if isinstance(columns, str):
+            raise ValueError('SpriteTable: columns is a tuple of names, not one string')
+        self._layers = None if layers is None else _rows.check_layers('SpriteTable', layers)
         self._columns = tuple(columns)
         if not self._columns:
             raise ValueError('SpriteTable: no columns')
@@ -60,12 +60,7 @@ class SpriteTable(object):
                                  % (c, ', '.join(self.ALL_COLUMNS)))
         if len(set(self._columns)) != len(self._columns):
             raise ValueError('SpriteTable: a column is named twice in %r' % (self._columns,))
-        if self._layers is not None and len(set(self._layers)) != len(self._layers):
-            raise ValueError('SpriteTable: a layer is named twice in %r' % (self._layers,))
-        dtype = np.dtype(dtype).name
-        if dtype not in _DTYPES:
-            raise ValueError("SpriteTable: dtype must be 'float32' or 'float16', got %r" % (dtype,))
-        self._dtype = dtype
+        self._dtype = _rows.check_dtype('SpriteTable', dtype)
         self._table = None   # the last lowering of this observer (compile_config), for observation_spec()
 
     @property
@@ -88,22 +83,11 @@ class SpriteTable(object):
                 raise ValueError('SpriteTable column%s %s: the state records hold scale / aspect_ratio only when the '
                                  'environment is built with keep_sprite_factors=True'
                                  % ('s' if len(need) > 1 else '', ', '.join(need)))
-        names = list(layer_names) if self._layers is None else list(self._layers)
+        slots, rows = _rows.layer_rows('SpriteTable', program, layer_names, self._layers)
         T = _abi.Table()
-        rows = []
-        for name in names:
-            if name not in layer_names:
-                raise ValueError('SpriteTable: unknown layer %r (the state has %s)' % (name, ', '.join(layer_names)))
-            li = list(layer_names).index(name)
-            s0, n = int(program.layer_slot0[li]), int(program.layer_nslots[li])
-            for k in range(n):
-                if len(rows) >= _abi.MOOG_MAX_SLOTS:
-                    raise ValueError('SpriteTable: more than %d rows' % _abi.MOOG_MAX_SLOTS)
-                T.row_slot[len(rows)] = s0 + k
-                rows.append((name, k))
-        if not rows:
-            raise ValueError('SpriteTable: the chosen layers hold no sprite slot')
-        T.n_rows, T.n_cols, T.dtype = len(rows), len(self._columns), _DTYPES[self._dtype]
+        for k, s in enumerate(slots):
+            T.row_slot[k] = s
+        T.n_rows, T.n_cols, T.dtype = len(rows), len(self._columns), _rows.DTYPES[self._dtype]
         for k, c in enumerate(self._columns):
             T.cols[k] = COLUMN_IDS[c]
         self._table = T

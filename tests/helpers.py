@@ -5,6 +5,7 @@ __graft_entry__.smoke() and bench.py's cpu_baseline leg load it.
 """
 import ctypes
 import functools
+import glob
 import os
 import subprocess
 
@@ -63,6 +64,21 @@ _bp = ctypes.POINTER(ctypes.c_uint8)
 
 def _ptr(a, t):
     return None if a is None else a.ctypes.data_as(t)
+
+
+def build_host_model(source, name):
+    """ctypes.CDLL of tests/_build/lib<name>.so: the host model `source` (a kernel header of csrc/ compiled with g++ and
+    walked lane by lane, tests/csrc/*.cpp), rebuilt when the source, include/moog_engine.h or any header of csrc/ is newer."""
+    build = os.path.join(REPO, 'tests', '_build')
+    os.makedirs(build, exist_ok=True)
+    so = os.path.join(build, 'lib%s.so' % name)
+    deps = [source, os.path.join(REPO, 'include', 'moog_engine.h')] + glob.glob(os.path.join(REPO, 'moog.github.io_amd', 'csrc', '*.h'))
+    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(p) for p in deps):
+        tmp = so + '.%d.tmp' % os.getpid()   # (xdist workers may build at the same time)
+        subprocess.check_call(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared', '-Wall',
+                               '-Wno-unused-function', source, '-o', tmp])
+        os.replace(tmp, so)
+    return ctypes.CDLL(so)
 
 
 @functools.lru_cache(maxsize=None)

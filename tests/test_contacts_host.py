@@ -19,9 +19,6 @@ from moog.observers import contacts as contacts_lib
 from moog_demos import example_configs
 
 SRC = os.path.join(helpers.REPO, 'tests', 'csrc', 'contacts_model.cpp')
-CORE = [os.path.join(helpers.REPO, 'moog.github.io_amd', 'csrc', h) for h in ('moog_contacts.h', 'moog_sprite_table.h')]
-BUILD = os.path.join(helpers.REPO, 'tests', '_build')
-SO = os.path.join(BUILD, 'libcontacts_model.so')
 RECORDINGS = ('colliding_predators_32', 'falling_balls_64', 'cleanup', 'pong')
 # (calls, ordered live pairs, past the circle, overlapping) as measured with matplotlib when the observer was specified
 COUNTS = {'colliding_predators_32': (41, 40672, 4542, 446), 'falling_balls_64': (13, 52416, 2612, 78),
@@ -30,14 +27,7 @@ PAIR, LAYER, VISIBLE = _abi.MOOG_CONTACTS_PAIR, _abi.MOOG_CONTACTS_LAYER, _abi.M
 
 
 def build_model():
-    os.makedirs(BUILD, exist_ok=True)
-    hdr = os.path.join(helpers.REPO, 'include', 'moog_engine.h')
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in [SRC, hdr] + CORE):
-        tmp = SO + '.%d.tmp' % os.getpid()   # (xdist workers may build at the same time)
-        subprocess.check_call(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared', '-Wall',
-                               '-Wno-unused-function', SRC, '-o', tmp])
-        os.replace(tmp, SO)
-    return ctypes.CDLL(SO)
+    return helpers.build_host_model(SRC, 'contacts_model')
 
 
 @pytest.fixture(scope='module')

@@ -14,22 +14,11 @@ import helpers
 from moog import _abi
 
 SRC = os.path.join(helpers.REPO, 'tests', 'csrc', 'raster_mask_model.cpp')
-CORE = os.path.join(helpers.REPO, 'moog.github.io_amd', 'csrc', 'moog_raster_mask_core.h')
-BUILD = os.path.join(helpers.REPO, 'tests', '_build')
-SO = os.path.join(BUILD, 'libraster_mask_model.so')
 _P = ctypes.POINTER
 
 
 def build_model():
-    os.makedirs(BUILD, exist_ok=True)
-    hdr = os.path.join(helpers.REPO, 'include', 'moog_engine.h')
-    draw = os.path.join(os.path.dirname(CORE), 'moog_draw_record.h')
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in (SRC, CORE, draw, hdr)):
-        tmp = SO + '.%d.tmp' % os.getpid()   # (xdist workers may build at the same time)
-        subprocess.check_call(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared', '-Wall',
-                               '-Wno-unused-function', SRC, '-o', tmp])
-        os.replace(tmp, SO)
-    return ctypes.CDLL(SO)
+    return helpers.build_host_model(SRC, 'raster_mask_model')
 
 
 @pytest.fixture(scope='module')

@@ -18,22 +18,12 @@ from moog import observers
 from moog_demos import example_configs
 
 SRC = os.path.join(helpers.REPO, 'tests', 'csrc', 'ray_sensor_model.cpp')
-CORE = [os.path.join(helpers.REPO, 'moog.github.io_amd', 'csrc', h) for h in ('moog_ray_sensor.h', 'moog_sprite_table.h')]
-BUILD = os.path.join(helpers.REPO, 'tests', '_build')
-SO = os.path.join(BUILD, 'libray_sensor_model.so')
 RECORDINGS = ('pong', 'colliding_predators_32', 'rules_zoo_l1', 'falling_balls_64')
 F32, F16 = _abi.MOOG_TABLE_F32, _abi.MOOG_TABLE_F16
 
 
 def build_model():
-    os.makedirs(BUILD, exist_ok=True)
-    hdr = os.path.join(helpers.REPO, 'include', 'moog_engine.h')
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in [SRC, hdr] + CORE):
-        tmp = SO + '.%d.tmp' % os.getpid()   # (xdist workers may build at the same time)
-        subprocess.check_call(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared', '-Wall',
-                               '-Wno-unused-function', SRC, '-o', tmp])
-        os.replace(tmp, SO)
-    return ctypes.CDLL(SO)
+    return helpers.build_host_model(SRC, 'ray_sensor_model')
 
 
 @pytest.fixture(scope='module')

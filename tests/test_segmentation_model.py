@@ -16,24 +16,13 @@ from moog_demos.example_configs import seg_zoo
 from test_raster_mask_model import random_polygon
 
 SRC = os.path.join(helpers.REPO, 'tests', 'csrc', 'segmentation_model.cpp')
-CSRC = os.path.join(helpers.REPO, 'moog.github.io_amd', 'csrc')
-BUILD = os.path.join(helpers.REPO, 'tests', '_build')
-SO = os.path.join(BUILD, 'libsegmentation_model.so')
 _P = ctypes.POINTER
 LEVELS = (0, 1, 2, 3, 4)
 CAPACITY = {4: {'prey': 8, 'predators': 8}}   # (the capacities level 4 was recorded with: the defaults, spelled out)
 
 
 def build_model():
-    os.makedirs(BUILD, exist_ok=True)
-    deps = [SRC, os.path.join(CSRC, 'moog_raster_mask_core.h'), os.path.join(CSRC, 'moog_draw_record.h'),
-            os.path.join(helpers.REPO, 'include', 'moog_engine.h')]
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in deps):
-        tmp = SO + '.%d.tmp' % os.getpid()   # (xdist workers may build at the same time)
-        subprocess.check_call(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared', '-Wall',
-                               '-Wno-unused-function', SRC, '-o', tmp])
-        os.replace(tmp, SO)
-    lib = ctypes.CDLL(SO)
+    lib = helpers.build_host_model(SRC, 'segmentation_model')
     lib.seg_model_plan_bytes.restype = ctypes.c_longlong
     return lib
 

@@ -19,9 +19,6 @@ from moog.observers import sprite_table
 from moog_demos import example_configs
 
 SRC = os.path.join(helpers.REPO, 'tests', 'csrc', 'sprite_table_model.cpp')
-CORE = os.path.join(helpers.REPO, 'moog.github.io_amd', 'csrc', 'moog_sprite_table.h')
-BUILD = os.path.join(helpers.REPO, 'tests', '_build')
-SO = os.path.join(BUILD, 'libsprite_table_model.so')
 ALL = observers.SpriteTable.ALL_COLUMNS
 DEFAULT = observers.SpriteTable.DEFAULT_COLUMNS
 # recordings the model packs: the three the tool measures and one whose rules append to layers (rules_zoo level 1:
@@ -30,14 +27,7 @@ RECORDINGS = ('pong', 'colliding_predators_32', 'chase_avoid_torus', 'rules_zoo_
 
 
 def build_model():
-    os.makedirs(BUILD, exist_ok=True)
-    hdr = os.path.join(helpers.REPO, 'include', 'moog_engine.h')
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in (SRC, CORE, hdr)):
-        tmp = SO + '.%d.tmp' % os.getpid()   # (xdist workers may build at the same time)
-        subprocess.check_call(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared', '-Wall',
-                               '-Wno-unused-function', SRC, '-o', tmp])
-        os.replace(tmp, SO)
-    return ctypes.CDLL(SO)
+    return helpers.build_host_model(SRC, 'sprite_table_model')
 
 
 @pytest.fixture(scope='module')
