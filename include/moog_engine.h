@@ -33,6 +33,7 @@ extern "C" {
  * bytes -- and with them their hashes and the names of the specialised step kernels -- stay put. */
 #define MOOG_PROGRAM_VERSION 30
 #define MOOG_MAX_ACTION_REPEAT 64 /* moog_engine_set_action_repeat: env-steps one call takes at most */
+#define MOOG_MAX_PLAN_CANDIDATES 1024 /* moog_engine_plan_sequences: action sequences per env one call evaluates at most */
 
 /* ---- capacity limits of the program blob -------------------------------- */
 #define MOOG_MAX_LAYERS 16
@@ -850,6 +851,37 @@ int moog_engine_set_action_repeat(moog_engine_t* e, int32_t k, int32_t* count_de
 int moog_engine_step_sequence(moog_engine_t* e, const void* actions_dev, int32_t n_steps, int64_t action_step_bytes,
                               double* rewards_dev, int64_t reward_step_elems, const moog_inject_t* inject,
                               const moog_step_out_t* out, void* hip_stream);
+/* Candidate rollouts (a planner's inner loop: random shooting, CEM / MPC): n_cand action sequences of n_steps env-steps for
+ * every env, all from the env's present record, in ONE kernel launch that reads each record n_cand times and writes none back
+ * -- one wavefront per (env, candidate), the whole record staged on chip.  Candidate k's outputs equal, bit for bit, those of
+ * moog_engine_step_sequence on its actions issued on this state; the state (both arrays, random counters included) and
+ * everything else the engine owns -- fault word, cost array and launch order, layer usage, reset pool, late-reset marks, the
+ * count buffer and outputs of moog_engine_step, draw records, tables, frames -- are as they were.  (With moog_engine_set_timing
+ * on, the launch is timed as MOOG_K_STEP.)
+ * actions_dev: block (k, j), laid out as moog_engine_step takes one and of the dtype moog_engine_set_action_dtype says, at
+ * actions_dev + k * action_cand_bytes + j * action_step_bytes.  rewards_dev: float64, the reward of step j of candidate k in env
+ * i at [k * reward_cand_elems + j * reward_step_elems + i]; 0.0 for the steps not taken.  count_dev (int32) / ended_dev (uint8)
+ * at [k * count_cand_elems + i]: the env-steps candidate k took in env i; 1 when the last of them asked for a reset.  The
+ * strides let a sub-batch read and write its slice of whole-batch arrays in place.  Every table with a trajectory bound
+ * (moog_engine_set_table_trajectory: its buffer and step_elems) is recorded per candidate, candidate k's blocks
+ * traj_cand_elems[table] elements behind candidate k - 1's (an array of MOOG_MAX_TABLES entries indexed by table; may be NULL
+ * when no trajectory is bound); the blocks of the steps not taken hold zero bits.  The kernel writes every element of every
+ * output; nothing needs clearing.
+ * An env whose reset_next is set takes no step in any candidate (count 0, rewards 0.0, ended 0) and is not reset: the next
+ * moog_engine_step does that as always.  The candidates read the record's random counters as they stand: all of them see the
+ * same draws (common random numbers), and so does the real step that follows; a per-candidate stream offset is not available.
+ * A fault bit a candidate raises dies with its copy of the record.  Launches exactly one kernel: the generic candidate kernel
+ * of the program's variant, or the one compiled for the program (moog_engine_plan_kernel says which; with a profiling word or
+ * a watcher set, the generic one, as for steps).
+ * MOOG_E_INVALID: null engine / actions / rewards / count / ended, n_cand outside 1 .. MOOG_MAX_PLAN_CANDIDATES, n_steps
+ * outside 1 .. MOOG_MAX_ACTION_REPEAT, a stride shorter than the block it steps over, a bound trajectory without its stride;
+ * MOOG_E_UNSUPPORTED: an engine whose action repeat is above 1, a record that fits the LDS only with the step kernels' cuts.
+ * It takes no injected uniforms. */
+int moog_engine_plan_sequences(moog_engine_t* e, const void* actions_dev, int32_t n_cand, int32_t n_steps,
+                               int64_t action_cand_bytes, int64_t action_step_bytes, double* rewards_dev,
+                               int64_t reward_cand_elems, int64_t reward_step_elems, int32_t* count_dev, uint8_t* ended_dev,
+                               int64_t count_cand_elems, const int64_t* traj_cand_elems, void* hip_stream);
+int moog_engine_plan_kernel(moog_engine_t* e, int32_t* specialised);
 /* env.physics.step(env.state) only (tests/runtime_benchmark.py:101-107). */
 int moog_engine_physics_only(moog_engine_t* e, const moog_inject_t* inject,
                              void* hip_stream);

@@ -126,7 +126,13 @@ struct moog_engine {
   void* spec_handle = nullptr;   // a step kernel compiled for this very program (load_spec_kernel), or null
   void (*spec_launch)(int, size_t, hipStream_t, const KArgs*) = nullptr;
   int32_t xstack_off = 0;
-  FOp* d_fops = nullptr;        // flattened force list (moog_flatten_forces)
+  // candidate rollouts (moog_engine_plan_sequences): the LDS of one wavefront with the WHOLE record staged (hot_layout_uncut)
+  // and the expression stacks' place in it; a candidate kernel compiled for this very program (load_spec_plan_kernel), or null
+  size_t plan_lds = 0;
+  int32_t plan_xstack_off = 0;
+  void* spec_plan_handle = nullptr;
+  void (*spec_plan_launch)(int, size_t, hipStream_t, const KArgs*) = nullptr;
+  FOp* d_fops = nullptr;       // flattened force list (moog_flatten_forces)
   int32_t n_fops = 0;
   int32_t* watch = nullptr;     // section sampling (MOOG_WATCH=1): [n_envs][MOOG_WATCH_SECTIONS]
   int32_t watch_off = 0;
@@ -358,7 +364,8 @@ static int env_prefix_slots(const moog_program_t* p, int* nsv) {
 // run-time sampler, dynamic layers / + the rare components), whether its episodes are opened by the reset kernel behind the
 // step kernel (late reset), the LDS of one env and the register-allocation variant that follows from it.  Used by
 // moog_engine_create and, through moog_program_step_kernel, by the builder of program-specialised kernels (moog/_spec.py).
-struct StepVariant { bool dynamic_rules = false, maze_kernel = false, late_reset = false; int wps = 4; size_t step_lds = 0; int32_t xstack_off = 0; };
+struct StepVariant { bool dynamic_rules = false, maze_kernel = false, late_reset = false; int wps = 4; size_t step_lds = 0; int32_t xstack_off = 0;
+                     size_t plan_lds = 0; int32_t plan_xstack_off = 0; };   // (plan_*: the candidate kernels', the whole record staged)
 
 static StepVariant step_variant_of(const moog_program_t* prog) {
   StepVariant v;
@@ -371,6 +378,14 @@ static StepVariant step_variant_of(const moog_program_t* prog) {
     v.step_lds = (v.step_lds + 15) & ~(size_t)15;
     v.xstack_off = (int32_t)v.step_lds;
     v.step_lds += (size_t)prog->xstack_depth * 64 * 8;
+  }
+  // the same areas behind the uncut record (hot_layout_uncut: 3 S doubles and 3 S words more where the step kernels cut them)
+  v.plan_lds = (size_t)GL.f64_per_env * 8 + (size_t)GL.i32_per_env * 4 + (size_t)GL.S * 4 * 8 +
+               (size_t)((GL.S + 3) & ~3) * 4 + CAND_CAP * 2 + 128 + 64 * 8 + 16;
+  if (prog->xstack_depth > 0) {
+    v.plan_lds = (v.plan_lds + 15) & ~(size_t)15;
+    v.plan_xstack_off = (int32_t)v.plan_lds;
+    v.plan_lds += (size_t)prog->xstack_depth * 64 * 8;
   }
   for (int r = 0; r < prog->n_rules; ++r) {
     int k = prog->rules[r].kind;
@@ -453,6 +468,8 @@ static uint64_t program_hash(const moog_program_t* prog) {   // FNV-1a 64 over t
 // checked -- the digest of the kernel sources and flags it was built from, ABI, argument struct, variant, and the embedded
 // program byte for byte -- before it replaces the generic kernel.
 static void load_spec_kernel(moog_engine* e, const moog_program_t* prog);
+// ... and the candidate kernel compiled for it, plan_<hash>_d<variant>w<wps>.so beside that object, checked the same way
+static void load_spec_plan_kernel(moog_engine* e, const moog_program_t* prog);
 
 // The digest of the kernel sources and flags this library was built from (moog/_digest.py; -DMOOG_SRC_DIGEST=0x...ull on the
 // command line of this unit and of every program-specialised step kernel).  0: built without one -- no specialised kernel loads.
@@ -882,6 +899,7 @@ int moog_engine_create(const moog_program_t* prog, int32_t n_envs, int32_t devic
   {
     const StepVariant sv = step_variant_of(prog);
     e->step_lds = sv.step_lds; e->xstack_off = sv.xstack_off;
+    e->plan_lds = sv.plan_lds; e->plan_xstack_off = sv.plan_xstack_off;
   }
   { const char* w = getenv("MOOG_WATCH");   // section sampling (moog_engine_read_watch): two words of LDS for the watcher
     if (w && atoi(w) == 1) {
@@ -912,12 +930,18 @@ int moog_engine_create(const moog_program_t* prog, int32_t n_envs, int32_t devic
                                           moog_configure_step_f3rt, moog_configure_step_f4rt, moog_configure_step_t3rt,
                                           moog_configure_step_t4rt, moog_configure_step_m3rt, moog_configure_step_m4rt};
     for (int v = 0; v < 18 && err == hipSuccess; ++v) err = (hipError_t)configure[v](e->step_lds);
+    // the candidate kernels stage the whole record: a record that fits only with its cuts steps, and refuses to plan
+    int (*const configure_plan[6])(size_t) = {moog_configure_step_f3rp, moog_configure_step_f4rp, moog_configure_step_t3rp,
+                                               moog_configure_step_t4rp, moog_configure_step_m3rp, moog_configure_step_m4rp};
+    if (e->plan_lds > 160 * 1024) e->plan_lds = 0;
+    for (int v = 0; v < 6 && e->plan_lds && err == hipSuccess; ++v) err = (hipError_t)configure_plan[v](e->plan_lds);
   }
   {
     const StepVariant sv = step_variant_of(prog);
     e->dynamic_rules = sv.dynamic_rules; e->maze_kernel = sv.maze_kernel; e->late_reset = sv.late_reset; e->step_wps = sv.wps;
   }
   if (!e->watch) load_spec_kernel(e, prog);
+  if (!e->watch && e->plan_lds) load_spec_plan_kernel(e, prog);
   if (e->late_reset) {
     if (hipMalloc(&e->late_mask, (size_t)n_envs) != hipSuccess || hipMemset(e->late_mask, 0, (size_t)n_envs) != hipSuccess) {
       free_engine(e);
@@ -1051,6 +1075,8 @@ static KArgs make_args(moog_engine* e, const void* actions, const moog_inject_t*
   a.repeat_count = mode == MODE_STEP ? e->repeat_count : nullptr;
   a.act_step_bytes = 0; a.reward_seq = nullptr; a.reward_seq_stride = 0;   // (moog_engine_step_sequence sets the three)
   memset(a.traj, 0, sizeof a.traj);   // (... and the trajectories bound with moog_engine_set_table_trajectory: no other call records)
+  a.n_cand = 0; a.act_cand_bytes = 0; a.reward_cand_stride = 0; a.plan_count = nullptr; a.plan_ended = nullptr;   // (moog_engine_plan_sequences)
+  a.count_cand_stride = 0; memset(a.traj_cand_elems, 0, sizeof a.traj_cand_elems);
   a.xstack_off = e->xstack_off;
   a.watch = (mode == MODE_STEP) ? e->watch : nullptr; a.watch_off = e->watch_off;
   a.fops = e->d_fops; a.n_fops = e->n_fops;
@@ -1444,6 +1470,76 @@ int moog_engine_step_sequence(moog_engine_t* e, const void* actions_dev, int32_t
   if (e->action_repeat > 1)
     return fail(MOOG_E_UNSUPPORTED, "an action sequence on an engine with an action repeat above 1 (a hold count per entry) is not available: moog_engine_set_action_repeat(e, 1, ...) first");
   return step_call(e, actions_dev, n_steps, action_step_bytes, rewards_dev, reward_step_elems, inject, out, hip_stream);
+}
+
+static bool plans_specialised(const moog_engine* e) { return e->spec_plan_launch && e->step_dbg == 0 && !e->watch; }
+
+int moog_engine_plan_sequences(moog_engine_t* e, const void* actions_dev, int32_t n_cand, int32_t n_steps,
+                               int64_t action_cand_bytes, int64_t action_step_bytes, double* rewards_dev,
+                               int64_t reward_cand_elems, int64_t reward_step_elems, int32_t* count_dev, uint8_t* ended_dev,
+                               int64_t count_cand_elems, const int64_t* traj_cand_elems, void* hip_stream) {
+  int rc = ready(e);
+  if (rc) return rc;
+  if (!actions_dev) return fail(MOOG_E_INVALID, "null actions");
+  if (!rewards_dev) return fail(MOOG_E_INVALID, "null rewards");
+  if (!count_dev || !ended_dev) return fail(MOOG_E_INVALID, "null count / ended");
+  if (n_cand < 1 || n_cand > MOOG_MAX_PLAN_CANDIDATES)
+    return fail(MOOG_E_INVALID, "candidate count out of range (1 .. MOOG_MAX_PLAN_CANDIDATES)");
+  if (n_steps < 1 || n_steps > MOOG_MAX_ACTION_REPEAT)
+    return fail(MOOG_E_INVALID, "sequence length out of range (1 .. MOOG_MAX_ACTION_REPEAT)");
+  if (action_cand_bytes < 0 || action_step_bytes < 0 || reward_step_elems < e->n_envs ||
+      reward_cand_elems < (int64_t)(n_steps - 1) * reward_step_elems + e->n_envs || count_cand_elems < e->n_envs)
+    return fail(MOOG_E_INVALID, "candidate rollouts: a stride is shorter than the block it steps over");
+  if ((int64_t)e->n_envs * n_cand > 0x7fffffffll) return fail(MOOG_E_INVALID, "candidate rollouts: n_envs x n_cand exceeds the grid");
+  if (e->action_repeat > 1)
+    return fail(MOOG_E_UNSUPPORTED, "candidate rollouts on an engine with an action repeat above 1 (a hold count per entry) are not available: moog_engine_set_action_repeat(e, 1, ...) first");
+  if (!e->plan_lds) return fail(MOOG_E_UNSUPPORTED, "candidate rollouts stage the whole record: this program's does not fit in 160 KB of LDS with the fields the step kernels leave in HBM");
+  hipStream_t s = (hipStream_t)hip_stream;
+  // MODE_STEP arguments, then everything a candidate must not touch taken out: no outputs, no cost, no pool, no late mask, no
+  // count buffer, no watcher, no usage counters, no draw record; the record's layout in LDS is the uncut one
+  KArgs a = make_args(e, actions_dev, nullptr, nullptr, MODE_STEP, nullptr);
+  a.H = hot_layout_uncut(e->L);
+  a.xstack_off = e->plan_xstack_off;
+  a.cost = nullptr; a.pool_state = nullptr; a.late_mask = nullptr; a.repeat_count = nullptr; a.watch = nullptr;
+  a.layer_hw = nullptr; a.fault_flag = nullptr;
+  a.repeat = n_steps;
+  a.act_step_bytes = action_step_bytes;
+  a.reward_seq = rewards_dev;
+  a.reward_seq_stride = reward_step_elems;
+  a.n_cand = n_cand;
+  a.act_cand_bytes = action_cand_bytes;
+  a.reward_cand_stride = reward_cand_elems;
+  a.plan_count = count_dev; a.plan_ended = ended_dev; a.count_cand_stride = count_cand_elems;
+  int n_traj = 0;   // (the tables with a trajectory first, as in step_call)
+  for (int k = 0; k < e->tables.n; ++k) {
+    const TrajTable& t = e->tables.at[k].traj;
+    if (!t.out) continue;
+    const int64_t block = (int64_t)e->n_envs * t.n_rows * (int64_t)t.n_cols;
+    if (!traj_cand_elems || traj_cand_elems[k] < (int64_t)(n_steps - 1) * t.step_elems + block)
+      return fail(MOOG_E_INVALID, "candidate rollouts: a bound trajectory needs its candidate stride (traj_cand_elems[table] >= (n_steps - 1) x step_elems + n_envs x n_rows x n_cols)");
+    a.traj_cand_elems[n_traj] = traj_cand_elems[k];
+    a.traj[n_traj++] = t;
+  }
+  if (e->sched_pending) HIPCHK(hipStreamWaitEvent(s, e->ev_sched_done, 0));   // (the launch order is read: not while the sort writes it)
+  {
+    Bracket br(e, MOOG_K_STEP, s);
+    const int blocks = e->n_envs * n_cand;
+    if (plans_specialised(e)) e->spec_plan_launch(blocks, e->plan_lds, s, &a);
+    else {
+      static const moog_step_launch_fn launch[6] = {moog_launch_step_f3rp, moog_launch_step_f4rp, moog_launch_step_t3rp,
+                                                    moog_launch_step_t4rp, moog_launch_step_m3rp, moog_launch_step_m4rp};
+      const bool full = e->maze_kernel && !e->late_reset;
+      launch[(full ? 4 : (e->dynamic_rules ? 2 : 0)) + (e->step_wps == 4 ? 1 : 0)](blocks, e->plan_lds, s, a);
+    }
+  }
+  HIPCHK(hipGetLastError());
+  return MOOG_OK;
+}
+
+int moog_engine_plan_kernel(moog_engine_t* e, int32_t* specialised) {
+  if (!e || !specialised) return fail(MOOG_E_INVALID, "null argument");
+  *specialised = plans_specialised(e) ? 1 : 0;
+  return MOOG_OK;
 }
 
 int moog_engine_physics_only(moog_engine_t* e, const moog_inject_t* inject, void* hip_stream) {
@@ -1935,24 +2031,27 @@ int moog_engine_kernel_time(moog_engine_t* e, int32_t kernel_id, double* total_m
 
 }  // extern "C"
 
-static void load_spec_kernel(moog_engine* e, const moog_program_t* prog) {
-  { const char* sw = getenv("MOOG_STEP_SPEC"); if (sw && atoi(sw) == 0) return; }   // 0: the generic kernels (A/B runs, tests)
+// One object of the spec directory: <prefix>_<hash>_d<variant>w<wps>.so, its configure function called with `lds`.  Returns the
+// launch function (and the handle), or null with the reason on stderr.
+static void* load_spec_object(moog_engine* e, const moog_program_t* prog, const char* prefix, const char* configure_name,
+                              const char* launch_name, size_t lds, void** handle) {
+  { const char* sw = getenv("MOOG_STEP_SPEC"); if (sw && atoi(sw) == 0) return nullptr; }   // 0: the generic kernels (A/B runs, tests)
   std::string dir;
   if (const char* d = getenv("MOOG_SPEC_DIR")) dir = d;
   else {
     Dl_info info;
-    if (!dladdr(reinterpret_cast<const void*>(&moog_abi_version), &info) || !info.dli_fname) return;
+    if (!dladdr(reinterpret_cast<const void*>(&moog_abi_version), &info) || !info.dli_fname) return nullptr;
     dir = info.dli_fname;
     const size_t cut = dir.find_last_of('/');
     dir = (cut == std::string::npos ? std::string(".") : dir.substr(0, cut)) + "/spec";
   }
   const bool full = e->maze_kernel && !e->late_reset;
   char name[96];
-  snprintf(name, sizeof name, "/step_%016llx_d%dw%d.so", (unsigned long long)program_hash(prog), full ? 2 : (e->dynamic_rules ? 1 : 0), e->step_wps);
+  snprintf(name, sizeof name, "/%s_%016llx_d%dw%d.so", prefix, (unsigned long long)program_hash(prog), full ? 2 : (e->dynamic_rules ? 1 : 0), e->step_wps);
   const std::string path = dir + name;
-  if (access(path.c_str(), R_OK) != 0) return;
+  if (access(path.c_str(), R_OK) != 0) return nullptr;
   void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-  if (!h) { fprintf(stderr, "moog: %s does not load (%s); the generic step kernel is used\n", path.c_str(), dlerror()); return; }
+  if (!h) { fprintf(stderr, "moog: %s does not load (%s); the generic step kernel is used\n", path.c_str(), dlerror()); return nullptr; }
   typedef int (*fn_i)(void);
   typedef unsigned long long (*fn_u)(void);
   typedef const void* (*fn_p)(void);
@@ -1966,19 +2065,29 @@ static void load_spec_kernel(moog_engine* e, const moog_program_t* prog) {
             "kernel is used -- rebuild it (python -m moog._spec ..., __graft_entry__.build())\n", path.c_str(),
             dig ? dig() : 0ull, (unsigned long long)MOOG_SRC_DIGEST);
     dlclose(h);
-    return;
+    return nullptr;
   }
   fn_p pr = reinterpret_cast<fn_p>(dlsym(h, "moog_spec_program"));
-  fn_cfg cfg = reinterpret_cast<fn_cfg>(dlsym(h, "moog_spec_configure"));
-  void* launch = dlsym(h, "moog_spec_launch");
+  fn_cfg cfg = reinterpret_cast<fn_cfg>(dlsym(h, configure_name));
+  void* launch = dlsym(h, launch_name);
   const bool ok = abi && var && hash && ksz && pr && cfg && launch && abi() == MOOG_ABI_VERSION && ksz() == sizeof(KArgs) &&
                   var() == ((full ? 2 : (e->dynamic_rules ? 1 : 0)) | (e->step_wps << 8)) && hash() == program_hash(prog) &&
-                  memcmp(pr(), prog, sizeof(moog_program_t)) == 0 && cfg(e->step_lds) == (int)hipSuccess;
+                  memcmp(pr(), prog, sizeof(moog_program_t)) == 0 && cfg(lds) == (int)hipSuccess;
   if (!ok) {
     fprintf(stderr, "moog: %s was built for another program, variant or ABI; the generic step kernel is used\n", path.c_str());
     dlclose(h);
-    return;
+    return nullptr;
   }
-  e->spec_handle = h;
+  *handle = h;
+  return launch;
+}
+
+static void load_spec_kernel(moog_engine* e, const moog_program_t* prog) {
+  void* launch = load_spec_object(e, prog, "step", "moog_spec_configure", "moog_spec_launch", e->step_lds, &e->spec_handle);
   e->spec_launch = reinterpret_cast<void (*)(int, size_t, hipStream_t, const KArgs*)>(launch);
+}
+
+static void load_spec_plan_kernel(moog_engine* e, const moog_program_t* prog) {
+  void* launch = load_spec_object(e, prog, "plan", "moog_spec_configure_3", "moog_spec_launch_3", e->plan_lds, &e->spec_plan_handle);
+  e->spec_plan_launch = reinterpret_cast<void (*)(int, size_t, hipStream_t, const KArgs*)>(launch);
 }

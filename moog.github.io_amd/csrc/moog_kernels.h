@@ -59,11 +59,26 @@ __host__ __device__ inline HotLayout hot_layout(const moog_layout_t& G) {
   return h;   // o_color / o_opacity / o_shape keep their values: valid in LDS when nothing was cut
 }
 
+// The hot layout with empty cuts: the whole record staged, colours, opacities, shape ids and Portal bits included.  What the
+// candidate kernels take (moog_plan_step_kernel): COL_SET / OPAC_SET / SHAPEID_SET / TELE_SET write wherever bind_env points
+// gcol / gopa / gshape / gtele, and with nothing cut that is LDS -- K wavefronts share one live record and none may write it.
+__host__ __device__ inline HotLayout hot_layout_uncut(const moog_layout_t& G) {
+  HotLayout h;
+  h.L = G;
+  h.f_cut0 = h.f_cut1 = G.o_color;
+  h.i_cut0 = h.i_cut1 = G.o_opacity;
+  return h;
+}
+
 #ifdef MOOG_SPEC_PROGRAM_INC
 __device__ __forceinline__ moog_layout_t moog_spec_hot_layout_fn() {
   moog_layout_t L;
   moog_layout(&MOOG_SPEC_PROGRAM, &L);
+#ifdef MOOG_SPEC_UNCUT   // (the unit of the candidate kernel, moog_step_spec.hip MOOG_SPEC_KERNEL == 3)
+  return L;
+#else
   return hot_layout(L).L;
+#endif
 }
 #endif
 
@@ -187,6 +202,18 @@ struct KArgs {
   // call every table here gets the env's rows as they are then, at block j; the blocks of the steps an env does not take hold
   // zero bits.  The tables in use come first: traj[0].out == null means that nothing is recorded.
   TrajTable traj[MOOG_MAX_TABLES];
+  // candidate rollouts (moog_engine_plan_sequences; read by moog_plan_step_kernel only): n_cand action sequences per env, one
+  // wavefront per (env, candidate).  Candidate k reads step j's action block at actions + k * act_cand_bytes + j * act_step_bytes,
+  // stores its reward to reward_seq[k * reward_cand_stride + j * reward_seq_stride + env], the env-steps it took and whether the
+  // last one asked for a reset to plan_count / plan_ended[k * count_cand_stride + env], and records table t's block of step j
+  // traj_cand_elems[t] elements behind candidate k - 1's.  The kernel adds k's offsets to its own copy of these arguments.
+  int32_t n_cand;
+  int64_t act_cand_bytes;
+  int64_t reward_cand_stride;
+  int32_t* plan_count;
+  uint8_t* plan_ended;
+  int64_t count_cand_stride;
+  int64_t traj_cand_elems[MOOG_MAX_TABLES];
 };
 
 enum { MODE_STEP = 0, MODE_PHYSICS = 1, MODE_RESET_MASK = 2, MODE_FILL = 3 };
@@ -781,19 +808,35 @@ __device__ __forceinline__ double uni_f64(double x) {
 // the REPEAT ones, launched only when a trajectory is bound.  Inside the REPEAT kernels, behind a wave-uniform test, the
 // recorder took the plain one's frame from 48 B / 17 spilled VGPRs to 136 B / 24 -- the sequences and repeats that record
 // nothing would have paid for it (DESIGN 3.1 "Rollout trajectories"); this way they keep the code they had.
-template <bool DYN, bool REPEAT, bool RECORD = false>
+// PLAN = the instantiation evaluates one candidate action sequence of the env from its live record and writes nothing back
+// (moog_engine_plan_sequences, moog_plan_step_kernel below): the REPEAT loop and the recorder as they are, between a prologue
+// that stages the WHOLE record (a.H has empty cuts: the fields the others write to HBM are in LDS here) and an epilogue that
+// stores the candidate's count and flag and nothing else.  Every global store reachable from here is either not compiled
+// (store_record, emit_draw_record, the auto-reset branch with the pool and the late mask, the timestep outputs, the cost, the
+// profiling words, the physics-only mode) or null (Env::layer_hw); the stores that remain go to reward_seq, plan_count,
+// plan_ended and the bound trajectories, at this candidate's places.  An env whose reset_next is set takes no step.
+template <bool DYN, bool REPEAT, bool RECORD = false, bool PLAN = false>
 __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned char* lds, const int lane) {
   static_assert(REPEAT || !RECORD, "the recorder sits in the repeat loop");
-  const long long t_sched = a.cost ? clock64() : 0;
+  static_assert(!PLAN || (REPEAT && RECORD), "a candidate kernel is a recording sequence kernel");
+  const long long t_sched = (!PLAN && a.cost) ? clock64() : 0;
   int32_t* gq = a.i32 + (size_t)env * a.L.i32_per_env;
   Env e;
   bind_env(e, a, env, lds, lane);
+  if constexpr (PLAN) e.layer_hw = nullptr;   // (the layers' usage counters are the engine's: a candidate's appends are not demand)
   const long long t_begin = (KDBG(a) & 128) ? clock64() : 0;
   double* gf = a.f64 + (size_t)env * a.L.f64_per_env;
   { PROF_T0; load_record(e, a.H, a.L, gf, gq); PROF_ADD(e, 9); }
   if (e.inj && e.lane == 0) EQ(e)[EL(e).o_rng + 2] = 0;
   wsync();
-  if (a.mode == MODE_STEP && uni(EQ(e)[EL(e).o_reset_next]) == 1) {   // auto-reset (environment.py:100-101)
+  if constexpr (PLAN) {
+    if (uni(EQ(e)[EL(e).o_reset_next]) == 1) {   // the next real step resets this env: no candidate has a step to take
+      if (e.lane == 0) { a.plan_count[env] = 0; a.plan_ended[env] = 0; }
+      reward_seq_zero(a, env, e.lane, 0);
+      traj_zero(a, env, e.lane, 0);
+      return;
+    }
+  } else if (a.mode == MODE_STEP && uni(EQ(e)[EL(e).o_reset_next]) == 1) {   // auto-reset (environment.py:100-101)
     int held = 0;
     if (!(DYN && pool_adopt(e, a, env, gf, gq, &held))) {   // (the next episode may be waiting in the reset pool)
       if (DYN && a.late_mask) {
@@ -844,7 +887,7 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
   for (;;) {
     if constexpr (REPEAT) { e.cell_tab_n = 0; e.cell_nw = 0; }   // (as bind_env leaves them)
     { PROF_T0; bbox_build_all(e); PROF_ADD(e, 9); }
-    if (a.mode == MODE_PHYSICS) {
+    if (!PLAN && a.mode == MODE_PHYSICS) {
       for (int k = 0; k < K; ++k) apply_physics<DYN>(e);
       store_record(e, a.H, a.L, gf, gq, a.fault_flag);
       return;
@@ -900,6 +943,12 @@ __device__ __forceinline__ void step_env(const KArgs& a, const int env, unsigned
     rj = uni_f64(rj);
     rsum = done == 0 ? rj : uni_f64(rsum + rj);   // ((r_1 + r_2) + ...) + r_m, in float64
     if (++done >= reps || sr) break;
+  }
+  if constexpr (PLAN) {   // the candidate's outputs; the record dies with the wavefront
+    if (e.lane == 0) { a.plan_count[env] = done; a.plan_ended[env] = sr ? 1 : 0; }
+    reward_seq_zero(a, env, e.lane, done);
+    traj_zero(a, env, e.lane, done);
+    return;
   }
   if (e.lane == 0) {
     if (sr) EQ(e)[EL(e).o_reset_next] = 1;
@@ -970,6 +1019,40 @@ __global__ __launch_bounds__(MOOG_STEP_THREADS, WPS) void moog_step_kernel(KArgs
 #endif
 }
 
+// Candidate rollouts (moog_engine_plan_sequences): one wavefront per (env, candidate), n_envs x n_cand workgroups.  Workgroup b
+// serves candidate b % n_cand of the env of launch rank b / n_cand (one scalar division per wavefront), so the K wavefronts
+// of an env are dispatched next to each other and the record's second to K-th loads find it in L2; a two-dimensional grid
+// (candidate in x, rank in y) would dispatch in the same order but caps the batch at 65535 envs.  The envs are taken in the
+// cost order when one is set (a.perm, read only).  The candidate's offsets go into this wavefront's copy of the arguments
+// (constant indices throughout: see TrajTable), and step_env<.., PLAN> runs the sequence on a record it never stores.
+template <bool DYN, int WPS, int VARIANT>   // VARIANT only names the instantiation (one per translation unit)
+__global__ __launch_bounds__(MOOG_STEP_THREADS, WPS) void moog_plan_step_kernel(KArgs a) {
+  const unsigned b = blockIdx.x, nc = (unsigned)a.n_cand;
+  const unsigned rank = b / nc;
+  const long long cand = (long long)(b - rank * nc);
+  int env = (int)rank;
+  if (env >= a.n_envs) return;
+  if (threadIdx.x >= 64) return;   // (a MOOG_WATCH build launches a watcher wavefront: the candidates have none)
+  if (a.perm) env = a.perm[env];
+#ifdef MOOG_SPEC_PROGRAM_INC
+  {   // a program-specialised build (moog_step_spec.hip): the layout is a compile-time constant like the program itself
+    moog_layout_t L;
+    moog_layout(&MOOG_SPEC_PROGRAM, &L);
+    a.L = L;
+    a.H = hot_layout_uncut(L);
+  }
+#endif
+  a.actions = static_cast<const char*>(a.actions) + cand * a.act_cand_bytes;
+  a.reward_seq += cand * a.reward_cand_stride;
+  a.plan_count += cand * a.count_cand_stride;
+  a.plan_ended += cand * a.count_cand_stride;
+#define MOOG_PLAN_TRAJ(t_) \
+  if (a.traj[t_].out) a.traj[t_].out = static_cast<char*>(a.traj[t_].out) + cand * a.traj_cand_elems[t_] * (a.traj[t_].dtype == MOOG_TABLE_F16 ? 2 : 4)
+  MOOG_PLAN_TRAJ(0); MOOG_PLAN_TRAJ(1); MOOG_PLAN_TRAJ(2); MOOG_PLAN_TRAJ(3);
+#undef MOOG_PLAN_TRAJ
+  step_env<DYN, true, true, true>(a, env, moog_lds, (int)threadIdx.x);
+}
+
 
 // ---- launch functions (one translation unit each, so that they compile in parallel) ------------------
 // variant = (dynamic rules ? 2 : 0) + (waves per SIMD == 4 ? 1 : 0); the ...r functions: the kernels with the action-repeat loop;
@@ -993,6 +1076,20 @@ void moog_launch_step_t3rt(int n_envs, size_t lds, hipStream_t s, const KArgs& a
 void moog_launch_step_t4rt(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 void moog_launch_step_m3rt(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
 void moog_launch_step_m4rt(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
+// (the ...rp functions: the candidate kernels, moog_plan_step_kernel; their first argument is the number of workgroups,
+//  n_envs x n_cand, and their LDS the uncut record's)
+void moog_launch_step_f3rp(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
+void moog_launch_step_f4rp(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
+void moog_launch_step_t3rp(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
+void moog_launch_step_t4rp(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
+void moog_launch_step_m3rp(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
+void moog_launch_step_m4rp(int n_envs, size_t lds, hipStream_t s, const KArgs& a);
+int moog_configure_step_f3rp(size_t lds);
+int moog_configure_step_f4rp(size_t lds);
+int moog_configure_step_t3rp(size_t lds);
+int moog_configure_step_t4rp(size_t lds);
+int moog_configure_step_m3rp(size_t lds);
+int moog_configure_step_m4rp(size_t lds);
 int moog_configure_step_f3(size_t lds);
 int moog_configure_step_f4(size_t lds);
 int moog_configure_step_t3(size_t lds);

@@ -8,9 +8,15 @@
 // Three kernels, one per unit so that they compile side by side (MOOG_SPEC_KERNEL): 0 the one-step kernel, 1 the one with the
 // action-repeat loop for calls with KArgs::repeat > 1 and for action sequences (KArgs::reward_seq), 2 the one that also records
 // a sequence's trajectory (KArgs::traj).  Unit 0 carries the object's interface as well.
+// MOOG_SPEC_KERNEL=3 is the candidate kernel (moog_plan_step_kernel, moog_engine_plan_sequences): compiled beside the three, with
+// the uncut record as its compile-time layout (MOOG_SPEC_UNCUT), and linked into an object of its own, plan_<hash>_d<dyn>w<wps>.so,
+// with an interface of its own (the same checks, moog_spec_configure_3 / moog_spec_launch_3): step_<hash>_... keeps three kernels.
 #include <hip/hip_runtime.h>
 
 #define MOOG_WITH_MAZE (MOOG_STEP_DYN == 2)
+#if MOOG_SPEC_KERNEL == 3
+#define MOOG_SPEC_UNCUT 1
+#endif
 #include "moog_kernels.h"
 
 #ifndef MOOG_SRC_DIGEST
@@ -18,14 +24,14 @@
 #endif
 #define MOOG_STR2(x) #x
 #define MOOG_STR(x) MOOG_STR2(x)
-#if MOOG_SPEC_KERNEL == 0
+#if MOOG_SPEC_KERNEL == 0 || MOOG_SPEC_KERNEL == 3
 extern "C" const char moog_src_digest_marker[] = "MOOG_SRC_DIGEST=" MOOG_STR(MOOG_SRC_DIGEST);   // (read as text by moog/_digest.py)
 
 #endif
 
 extern "C" {
 
-#if MOOG_SPEC_KERNEL == 0
+#if MOOG_SPEC_KERNEL == 0 || MOOG_SPEC_KERNEL == 3
 
 // (moog/_digest.py: the kernel sources and flags this object was built from; the engine library refuses another build's)
 unsigned long long moog_spec_source_digest(void) { return MOOG_SRC_DIGEST; }
@@ -38,9 +44,13 @@ const void* moog_spec_program(void) { return &MOOG_SPEC_PROGRAM; }
 #endif
 
 #ifndef MOOG_SPEC_KERNEL
-#error "MOOG_SPEC_KERNEL=0|1|2: which of the object's three kernels this unit holds"
+#error "MOOG_SPEC_KERNEL=0|1|2: which of the object's three kernels this unit holds; 3: the candidate kernel"
 #endif
+#if MOOG_SPEC_KERNEL == 3
+#define MOOG_SPEC_THE_KERNEL moog_plan_step_kernel<MOOG_STEP_DYN != 0, MOOG_STEP_WPS, MOOG_STEP_DYN>
+#else
 #define MOOG_SPEC_THE_KERNEL moog_step_kernel<MOOG_STEP_DYN != 0, MOOG_STEP_WPS, MOOG_STEP_DYN, (MOOG_SPEC_KERNEL >= 1), (MOOG_SPEC_KERNEL >= 2)>
+#endif
 #define MOOG_CAT_(a, b) a##b
 #define MOOG_CAT(a, b) MOOG_CAT_(a, b)
 

@@ -27,6 +27,7 @@ SYMBOLS = (
     'moog_engine_add_contacts', 'moog_engine_set_contacts_buffer', 'moog_engine_observe_contacts',
     'moog_engine_add_segmentation', 'moog_engine_set_segmentation_image',
     'moog_engine_step_sequence', 'moog_engine_set_table_trajectory',
+    'moog_engine_plan_sequences', 'moog_engine_plan_kernel',
 )
 
 _LIB = None
@@ -72,6 +73,8 @@ def load_library(path=None):
                                      ctypes.POINTER(_abi.StepOut), vp]
     lib.moog_engine_step_sequence.argtypes = [vp, vp, i32, i64, vp, i64, ctypes.POINTER(_abi.Inject),
                                               ctypes.POINTER(_abi.StepOut), vp]
+    lib.moog_engine_plan_sequences.argtypes = [vp, vp, i32, i32, i64, i64, vp, i64, i64, vp, vp, i64, ctypes.POINTER(i64), vp]
+    lib.moog_engine_plan_kernel.argtypes = [vp, ctypes.POINTER(i32)]
     lib.moog_engine_physics_only.argtypes = [vp, ctypes.POINTER(_abi.Inject), vp]
     lib.moog_engine_render.argtypes = [vp, vp, vp]
     lib.moog_engine_set_schedule.argtypes = [vp, vp, vp]

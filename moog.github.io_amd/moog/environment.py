@@ -813,9 +813,10 @@ class BatchedEnvironment(object):
                 n, len(self.action_space.action_keys), n, n, list(self.action_space.action_keys))
         return '[T, %d]' % n if self._is_grid else '[T, %d, 2]' % n
 
-    def _pack_sequence(self, actions, n=None):
+    def _pack_sequence(self, actions, n=None, _blocks=False):
         """A rollout's actions as ONE device tensor [T, n, ...], step t's block laid out as step() hands one to the engine
-        (float32 Joystick actions stay float32).  ValueError: a shape or a dict key that does not fit, T out of range."""
+        (float32 Joystick actions stay float32).  ValueError: a shape or a dict key that does not fit, T out of range.
+        (_blocks: any number of blocks -- _pack_candidates packs its K x T of them here and checks the two ranges itself.)"""
         torch = self._torch
         n = self.num_envs if n is None else n
 
@@ -861,7 +862,7 @@ class BatchedEnvironment(object):
             if a.dim() != 3 or tuple(a.shape[1:]) != (n, 2):
                 raise bad(tuple(a.shape))
             a = a if a.dtype == torch.float32 else a.to(torch.float64)
-        if not 1 <= a.shape[0] <= _abi.MOOG_MAX_ACTION_REPEAT:
+        if not _blocks and not 1 <= a.shape[0] <= _abi.MOOG_MAX_ACTION_REPEAT:
             raise bad(tuple(a.shape))
         return a if a[0].is_contiguous() and (a.shape[0] == 1 or a.stride(0) >= a[0].numel()) else a.contiguous()
 
@@ -977,6 +978,133 @@ class BatchedEnvironment(object):
         self._last_action = a
         self._after_step_call(False)
         return self._timestep()
+
+    # -- candidate rollouts (include/moog_engine.h moog_engine_plan_sequences) -----------------
+    def plan_kernel(self):
+        """'specialised' when rollout_candidates runs a kernel compiled for this program (moog/_spec.py), else 'generic'."""
+        v = ctypes.c_int32()
+        _engine.check(self._lib, self._lib.moog_engine_plan_kernel(self._handle, ctypes.byref(v)))
+        return 'specialised' if v.value else 'generic'
+
+    @staticmethod
+    def _candidate_dims(actions):
+        """(K, T) of rollout_candidates' actions, from their shape alone."""
+        if isinstance(actions, dict):
+            actions = next(iter(actions.values())) if actions else ()
+        shape = tuple(actions.shape) if hasattr(actions, 'shape') else tuple(np.shape(actions))
+        if len(shape) < 3:
+            raise ValueError('rollout_candidates: actions of shape %s, expected a leading [K, T, num_envs]' % (shape,))
+        return int(shape[0]), int(shape[1])
+
+    def _check_candidates(self, K, T):
+        """(K, T), or the reason this engine cannot evaluate K sequences of T env-steps per env inside one launch."""
+        if not 1 <= K <= _abi.MOOG_MAX_PLAN_CANDIDATES:
+            raise ValueError('rollout_candidates: K = %d candidates per env, expected 1 .. %d' % (K, _abi.MOOG_MAX_PLAN_CANDIDATES))
+        return K, self._check_rollout(T)
+
+    def _pack_candidates(self, actions, n=None):
+        """rollout_candidates' actions as ONE contiguous device tensor [K, T, n, ...], block [k, t] laid out as step() hands
+        one to the engine (_pack_sequence over the K x T blocks)."""
+        torch = self._torch
+        n = self.num_envs if n is None else n
+        K, T = self._candidate_dims(actions)
+
+        def flat(v):
+            v = torch.as_tensor(v, device=self.device)
+            return v.reshape((K * T,) + tuple(v.shape[2:])) if v.dim() >= 2 and tuple(v.shape[:2]) == (K, T) else v
+
+        try:
+            a = self._pack_sequence({key: flat(v) for key, v in actions.items()} if isinstance(actions, dict) else flat(actions),
+                                    n, _blocks=True)
+        except ValueError as err:
+            if 'composite action keys' in str(err):
+                raise
+            got = ({key: tuple(np.shape(v)) if not hasattr(v, 'shape') else tuple(v.shape) for key, v in actions.items()}
+                   if isinstance(actions, dict) else (tuple(actions.shape) if hasattr(actions, 'shape') else tuple(np.shape(actions))))
+            raise ValueError('rollout_candidates: actions of shape %s, expected %s with 1 <= K <= %d and 1 <= T <= %d'
+                             % (got, self._sequence_shape(n).replace('[T, ', '[K, T, '), _abi.MOOG_MAX_PLAN_CANDIDATES,
+                                _abi.MOOG_MAX_ACTION_REPEAT)) from None
+        a = a.contiguous()
+        return a.reshape((K, T) + tuple(a.shape[1:]))
+
+    def _new_candidate_outputs(self, K, T, keys, n=None):
+        """(rewards [K, T, n] float64, count [K, n] int32, ended [K, n] uint8, {key: [K, T, n, rows, columns]} or None),
+        uninitialised: the candidate kernel writes every element."""
+        torch = self._torch
+        n = self.num_envs if n is None else n
+        with torch.cuda.device(self.device):
+            rewards = torch.empty((K, T, n), dtype=torch.float64, device=self.device)
+            count = torch.empty((K, n), dtype=torch.int32, device=self.device)
+            ended = torch.empty((K, n), dtype=torch.uint8, device=self.device)
+            traj = None if keys is None else {
+                key: torch.empty((K, T, n) + tuple(self.tables[key].shape[1:]), dtype=self.tables[key].dtype, device=self.device)
+                for key in keys}
+        return rewards, count, ended, traj
+
+    def rollout_candidates(self, actions, record=None):
+        """A planner's inner loop (random shooting, CEM / MPC): K action sequences of T env-steps for every env, all from the
+        env's present state, in ONE launch of a step kernel that reads each record K times and writes none back.
+        actions: rollout()'s layouts with a leading K -- [K, T, N, 2] (Joystick; float32 stays float32), [K, T, N] (Grid),
+        [K, T, N, n_spaces, 2] or a dict of [K, T, N, 2] / [K, T, N] (Composite); 1 <= T <= MOOG_MAX_ACTION_REPEAT,
+        1 <= K <= MOOG_MAX_PLAN_CANDIDATES.  Returns (rewards, count, ended):
+          rewards   float64 [K, T, N]: the reward of every env-step candidate k took in env e; 0.0 for the steps not taken
+          count     int32 [K, N]: the env-steps taken
+          ended     uint8 [K, N]: 1 when the candidate's last step taken asked for a reset
+        With record (a SpriteTable key or a list of keys, as in rollout()) a fourth value, trajectory = {key: a fresh tensor
+        [K, T, N, rows, columns] of the table's dtype}: block [k, j, e] is what rollout(actions[k], record=key) would put
+        in [j, e], zero bits for the steps not taken.
+        Candidate k's outputs equal, bit for bit, those of rollout(actions[k]) issued on this state.  The state (both
+        tensors, random counters included) is put back afterwards, and the call changes nothing.
+        So: an env whose reset_next is set takes no step in any candidate (count 0, rewards 0.0, ended 0) and is not reset --
+        the next real step() does that as always; the candidates read the record's random counters as they stand, so all K
+        see the same draws (common random numbers) and the real step that follows sees them too; host-side meta-state
+        rules do not run.  Refused, before anything touches a device and with rollout()'s error types: shapes that do not
+        fit, K or T out of range, action_repeat above 1, host-side rules with T > 1, layer_capacity='auto', record keys
+        that are no SpriteTable of the config."""
+        keys = None if record is None else self._check_record(record)   # (refusals first: they need no device)
+        K, T = self._check_candidates(*self._candidate_dims(actions))
+        a = self._pack_candidates(actions)
+        rewards, count, ended, traj = self._new_candidate_outputs(K, T, keys)
+        self._rollout_candidates_packed(a, rewards, count, ended, traj)
+        return (rewards, count, ended) if keys is None else (rewards, count, ended, traj)
+
+    def _rollout_candidates_packed(self, a, rewards, count, ended, traj=None):
+        """rollout_candidates() on packed actions [K, T, n, ...] and outputs of the caller's -- rewards [K, T, n], count and
+        ended [K, n], traj None or {SpriteTable key: [K, T, n, rows, columns]} -- any of them possibly a slice of a whole
+        batch's along the env axis: the engine takes the strides.  The trajectory tensors are bound before the call and
+        unbound behind it, as _rollout_packed does."""
+        torch = self._torch
+        K, T = self._check_candidates(int(a.shape[0]), int(a.shape[1]))
+        n = self.num_envs
+        assert a.shape[2] == n and a[0, 0].is_contiguous(), (tuple(a.shape), a.stride())
+        assert tuple(rewards.shape) == (K, T, n) and rewards.dtype == torch.float64 and rewards.stride(2) == 1
+        assert tuple(count.shape) == (K, n) and count.dtype == torch.int32 and count.stride(1) == 1
+        assert tuple(ended.shape) == (K, n) and ended.dtype == torch.uint8 and ended.stride() == count.stride()
+        strides = (ctypes.c_int64 * _abi.MOOG_MAX_TABLES)()
+        for key, t in (traj or {}).items():
+            own = self.tables[key]
+            assert tuple(t.shape) == (K, T, n) + tuple(own.shape[1:]) and t.dtype == own.dtype, (key, tuple(t.shape), t.dtype)
+            assert t[0, 0].is_contiguous() and t.stride(1) >= t[0, 0].numel(), (key, t.stride())
+            strides[self._table_index[key]] = t.stride(0)
+        if a.dtype != torch.int32 and not self._composite:
+            f32 = a.dtype == torch.float32
+            if f32 != self._action_f32:
+                _engine.check(self._lib, self._lib.moog_engine_set_action_dtype(self._handle, 1 if f32 else 0))
+                self._action_f32 = f32
+        if traj:
+            for key, t in traj.items():
+                _engine.check(self._lib, self._lib.moog_engine_set_table_trajectory(
+                    self._handle, self._table_index[key], ctypes.c_void_p(t.data_ptr()), t.stride(1)))
+        try:
+            with torch.cuda.device(self.device):
+                _engine.check(self._lib, self._lib.moog_engine_plan_sequences(
+                    self._handle, ctypes.c_void_p(a.data_ptr()), K, T, a.stride(0) * a.element_size(), a.stride(1) * a.element_size(),
+                    ctypes.c_void_p(rewards.data_ptr()), rewards.stride(0), rewards.stride(1),
+                    ctypes.c_void_p(count.data_ptr()), ctypes.c_void_p(ended.data_ptr()), count.stride(0),
+                    strides if traj else None, self._stream()))
+        finally:
+            if traj:   # (a later call without `record` must not write to this call's tensors)
+                self._bind_trajectory(dict.fromkeys(traj))
 
     def _pack_composite(self, action):
         """Composite actions (composite.py:51-62): a dict {key: tensor [N, 2] or, for a Grid
@@ -1396,6 +1524,27 @@ class SubBatchedEnvironment(object):
         if traj is None:
             return self._timestep(), rewards, self.repeat_count
         return self._timestep(), rewards, self.repeat_count, traj
+
+    def rollout_candidates(self, actions, record=None):
+        """BatchedEnvironment.rollout_candidates of the whole batch, synchronous: the actions are packed once, sub-batch g
+        evaluates its [:, :, g m:(g + 1) m] slice of them on its own stream and writes its slices of the whole-batch
+        outputs (no copies: the engine takes the strides), the caller's stream waits for all of them.  The results do not
+        depend on G, and no sub-batch's state changes."""
+        p0 = self.parts[0]
+        keys = None if record is None else p0._check_record(record)
+        K, T = p0._check_candidates(*p0._candidate_dims(actions))
+        a = p0._pack_candidates(actions, self.num_envs)
+        rewards, count, ended, traj = p0._new_candidate_outputs(K, T, keys, self.num_envs)
+        m = self.part_envs
+        for g in range(self.sub_batches):
+            for t in [a, rewards, count, ended] + list((traj or {}).values()):
+                t.record_stream(self._streams[g])
+            part = None if traj is None else {key: t[:, :, g * m:(g + 1) * m] for key, t in traj.items()}
+            self._enqueue(g, lambda g=g, part=part: self.parts[g]._rollout_candidates_packed(
+                a[:, :, g * m:(g + 1) * m], rewards[:, :, g * m:(g + 1) * m], count[:, g * m:(g + 1) * m],
+                ended[:, g * m:(g + 1) * m], part))
+        self._join()
+        return (rewards, count, ended) if traj is None else (rewards, count, ended, traj)
 
     def random_action(self):
         torch = self._torch
